@@ -1,7 +1,15 @@
 """Benchmark of RAMCloud's CRC32C integrity-checksum path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--config segments|recovery|entries|stream|replay|append|host]
+
+A plain run sets up, warms up, times exactly K steps and prints the result
+line.  --full adds everything that takes work of its own beside the timed
+steps: the CPU baselines, the comparisons of the GPU results with the
+reference / oracle / host CRC path, and the 1-GPU t1 run at N > 1; their
+fields are null without it.  --dump-outputs DIR writes what the last timed
+step returned to its caller as DIR/<name>.npy (float64; the inputs are seeded,
+so two builds can be compared output for output).
 
 Default (--config segments):
   N = 1  BASELINE config 2: 1024 x 8 MiB segments resident in HBM, one step =
@@ -21,7 +29,7 @@ Default (--config segments):
 Rank 0 prints one JSON line.  `roofline` prices the dominant kernel from its
 HIP-event duration on its launch stream; `traffic` is the corrected PMC
 FETCH_SIZE of that kernel measured on this exact workload (profiles/pmc/),
-or null when no such profile exists.  `cpu_baseline` (N = 1) times the
+or null when no such profile exists.  `cpu_baseline` (--full, N = 1) times the
 reference's compiled intelCrc32C (oracle/_ref) -- or the oracle restatement
 when _ref was not shipped -- over the same 8 GiB batch on this host's cores
 (1 thread and T = min(physical cores, cgroup CPU quota) threads, best and
@@ -152,6 +160,27 @@ def roofline(kernel, algo_bytes, kernel_ms, traffic_key):
             "traffic": traffic, "traffic_source": src,
             "avg_kernel_ms": round(kernel_ms, 4),
             "algorithmic_bytes_per_launch": algo_bytes, "traffic_key": traffic_key}
+
+
+# ------------------------------------------------------------- output dump
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(args, **arrays):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step,
+    one DIR/<name>.npy each, as float64 (exact for the uint32 CRCs and status
+    words).  All files together stay under DUMP_LIMIT_BYTES: a larger array
+    is cut down to a fixed, seeded sample of its elements (in index order)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 8 // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.size > budget:
+            idx = np.sort(np.random.default_rng(0x52414D43).choice(a.size, budget, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float64))
 
 
 # ------------------------------------------------------------ distributed
@@ -321,6 +350,7 @@ def run_c2(args, ranks):
     gpu = out.cpu().numpy().view(np.uint32)
     kat_ok = None
     if ranks.rank == 0:
+        dump_outputs(args, crcs=gpu)
         with open(os.path.join(ROOT, "tests", "golden", "crc32c_golden.json")) as f:
             kats = {k["name"]: k["crc"] for k in json.load(f)["kat"] if "crc" in k}
         kat_ok = all(int(gpu[i]) == kats[f"bench_segment_{i}"] for i in range(min(4, nseg)))
@@ -400,17 +430,21 @@ def run_recovery(args, ranks):
     shard.set_timing(False)
     avg_ms = kernel_ms / max(launches, 1)
     gathered = out.cpu().numpy().view(np.uint32)
-    # Full check of the gathered batch on every rank: each rank CRCs its own
-    # segments on the host (libramcrc's SSE4.2 path, independent of the
+    if ranks.rank == 0:
+        dump_outputs(args, crcs=gathered)
+    # Full check of the gathered batch on every rank (--full): each rank CRCs
+    # its own segments on the host (libramcrc's SSE4.2 path, independent of the
     # kernels), the per-rank lists are exchanged, and every rank compares all
     # `total` gathered CRCs with them.
-    mine = _host_segment_crcs(data, seg, count)
-    expect = np.zeros(total, np.uint32)
-    for q_lo, q_crcs in ranks.gather_objects((lo, mine.tobytes())):
-        q = np.frombuffer(q_crcs, np.uint32)
-        expect[q_lo:q_lo + q.size] = q
-    bad = int((gathered != expect).sum())
-    bad_per_rank = ranks.gather_objects(bad)
+    bad_per_rank = None
+    if args.full:
+        mine = _host_segment_crcs(data, seg, count)
+        expect = np.zeros(total, np.uint32)
+        for q_lo, q_crcs in ranks.gather_objects((lo, mine.tobytes())):
+            q = np.frombuffer(q_crcs, np.uint32)
+            expect[q_lo:q_lo + q.size] = q
+        bad = int((gathered != expect).sum())
+        bad_per_rank = ranks.gather_objects(bad)
     shard.close()
     # The reference's CPU path beside the GPU line, at every N (rank 0, outside
     # the timed region): intelCrc32C over the whole batch on this host's cores.
@@ -445,8 +479,9 @@ def run_recovery(args, ranks):
                    "exchange": "RCCL ncclAllGather of uint32 CRCs (libramcrc ramcrc_shard_segments)"},
         "roofline": roofline("k_chunks", count * seg, avg_ms, key),
         "cpu_baseline": cpu,
-        "bit_exact": all(b == 0 for b in bad_per_rank),
-        "bit_exact_check": (f"all {total} gathered CRCs on each of the {ranks.world} ranks vs "
+        "bit_exact": None if bad_per_rank is None else all(b == 0 for b in bad_per_rank),
+        "bit_exact_check": (None if bad_per_rank is None else
+                            f"all {total} gathered CRCs on each of the {ranks.world} ranks vs "
                             "each owner's host CRCs of its segments (libramcrc SSE4.2 path); "
                             f"mismatches per rank {bad_per_rank}"),
     }
@@ -537,6 +572,7 @@ def run_recovery_host_dry(args, ranks):
     if ranks.rank != 0:
         return None
     crcs = box["full"].numpy().view(np.uint32)
+    dump_outputs(args, crcs=crcs)
     cpu = None
     if not args.no_cpu_baseline:
         # as the GPU line: the reference's CPU path over the whole batch, rank 0
@@ -594,6 +630,7 @@ def run_entries(args, ranks):
         ctx.close()
         return None
     gpu = out.cpu().numpy().view(np.uint32)
+    dump_outputs(args, crcs=gpu)
     cpu = None if args.no_cpu_baseline else cpu_baseline_entries(host, offs, lens, gpu)
     scan_ms = kernel_ms / args.steps
     mix = "fixed %d B" % args.entry_size if args.entry_size else "100B/1KiB/4KiB Zipf"
@@ -798,6 +835,8 @@ def run_replay(args, ranks):
         ctx.set_timing(False)
         rv.check()
         sts = [box["st"]]
+    # the statuses the last timed step returned (pipelined: of its batch)
+    dump_outputs(args, status=sts[(args.steps - 1) % len(sts)].cpu().numpy().view(np.uint32))
     ok = True
     for st in sts:
         status = st.cpu().numpy().view(np.uint32)
@@ -865,7 +904,7 @@ def run_contexts(args, ranks):
     steps / wall time.  Every output of every context is checked: entries
     against the reference's intelCrc32C per entry, replay statuses and object
     CRCs against context 0's and context 0's first segments against the
-    oracle's walk and checksums.  bin_rescues: k_bin_one launches of each
+    oracle's walk and checksums (--full).  bin_rescues: k_bin_one launches of each
     context that aborted (grid not all resident in time) and were binned by
     the guarded scatter."""
     import threading
@@ -947,8 +986,14 @@ def run_contexts(args, ranks):
     for c in ctxs:
         c.check()
     rescues = [c.bin_rescues() for c in ctxs]
-    check = {}
     if args.config == "entries":
+        dump_outputs(args, crcs=outs[0].cpu().numpy().view(np.uint32))
+    else:
+        dump_outputs(args, status=sts[0].cpu().numpy().view(np.uint32))
+    check = {}
+    if not args.full:
+        check = {"all_crcs_match": None}
+    elif args.config == "entries":
         from oracle import oracle
         want = (oracle.ref_entries(host, offs, lens, threads=baseline_threads(host_cpu_info()))
                 if oracle.ref_available() else oracle.entries(host, offs, lens))
@@ -1018,6 +1063,7 @@ def run_append(args, ranks):
     ctx.check()
     credited = total - 4 * lens.size   # bytes [4, len) of every object
     got = out.cpu().numpy().view(np.uint32)
+    dump_outputs(args, crcs=got)
     stamped = data.cpu().numpy()
     hdr = stamped[(offs.astype(np.int64)[:, None] + np.arange(4)).reshape(-1)].reshape(-1, 4).copy().view("<u4")[:, 0]
     cpu = None
@@ -1062,6 +1108,7 @@ def run_stream(args, ranks):
 
     elapsed = timed(args.steps, 1, step, lambda: None, ranks)
     out = box["out"]
+    dump_outputs(args, crcs=np.asarray(out, dtype=np.uint32))
     a = host.numpy()
     spot = all(int(out[i]) == ramcrc.crc32c(a[i * seg:(i + 1) * seg]) for i in range(min(4, nseg)))
     ctx.close()
@@ -1141,12 +1188,25 @@ def parse_args(argv=None):
     ap.add_argument("--contexts", type=int, default=0,
                     help="entries / replay config: K host threads, one context and stream each, "
                          "submitting concurrently (RecoverSegmentBenchmark's replay threads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines, "
+                         "the checks of the GPU results against the reference / oracle / host "
+                         "path, and the 1-GPU t1 run at N>1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-reps", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-t1", action="store_true", help="config 4 at N>1: skip the 1-GPU t1 run")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-t1", action="store_true",
+                    help="with --full, config 4 at N>1: skip the 1-GPU t1 run")
     ap.add_argument("--host-dry-run", action="store_true",
                     help="config 4 plumbing on the CPU (gloo, host CRC path, no GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_t1 = True
+    return args
 
 
 def main():

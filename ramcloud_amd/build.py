@@ -96,14 +96,15 @@ def _stale():
 
 
 def _compile(out, defines=(), verbose=False):
+    # refused before anything is created or looked up
+    if unsafe_defines(defines):
+        raise ValueError(f"refusing a build with unsafe knobs: {unsafe_defines(defines)}")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     tmp = out + ".tmp"
     flags = _flags(defines)
     cmd = [hipcc()] + [f for f in flags if f != "-ldl"]
     cmd += ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
-    if unsafe_defines(defines):
-        raise ValueError(f"refusing a build with unsafe knobs: {unsafe_defines(defines)}")
-    cmd += [f'-DRAMCRC_SRC_SHA="{source_sha(defines)}"']
+    cmd +=[f'-DRAMCRC_SRC_SHA="{source_sha(defines)}"']
     if defines:
         cmd += [f'-DRAMCRC_DEFINES="{",".join(defines)}"']
     cmd += [os.path.join(CSRC, s) for s in SOURCES]

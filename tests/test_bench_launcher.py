@@ -26,7 +26,7 @@ def test_bench_spawns_ranks_and_gathers(oracle_mod, ramcrc):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                           "--host-dry-run", "--nseg-total", str(nseg), "--seg-kib", "64",
-                          "--value-len", str(vlen), "--steps", "2", "--warmup", "1"],
+                          "--value-len", str(vlen), "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = _json_line(out.stdout)
@@ -45,6 +45,24 @@ def test_bench_spawns_ranks_and_gathers(oracle_mod, ramcrc):
     cpu = line["cpu_baseline"]
     assert cpu["bit_exact_vs_gpu"] is True and cpu["cores"] >= 1 and cpu["value"] > 0
     assert cpu["kind"] in ("reference", "port")
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries no CPU baseline; --steps is the number
+    of timed steps; --dump-outputs writes the last step's CRCs as float64."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                          "--host-dry-run", "--nseg-total", "5", "--seg-kib", "64",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = _json_line(out.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None
+    assert [p.name for p in dump.iterdir()] == ["crcs.npy"]
+    crcs = np.load(dump / "crcs.npy")
+    assert crcs.dtype == np.float64 and crcs.tolist() == line["crcs"]
 
 
 def test_bench_refuses_world_mismatch():

@@ -29,11 +29,13 @@ def test_variant_knobs_exist_and_move():
             assert defaults[k] != v, f"{name}: {d} is the default"
 
 
-def test_no_unsafe_variant_and_build_refuses():
+def test_no_unsafe_variant_and_build_refuses(tmp_path):
     for name, defs in VARIANTS.items():
         assert not build.unsafe_defines(defs), name
+    out = tmp_path / "variants" / "lib.so"
     with pytest.raises(ValueError):
-        build._compile("/nonexistent/lib.so", ("RAMCRC_PROBE_FOLD=1",))
+        build._compile(str(out), ("RAMCRC_PROBE_FOLD=1",))
+    assert not out.parent.exists()   # refused before anything was created
 
 
 def test_build_info_defines_parsed():

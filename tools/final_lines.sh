@@ -12,23 +12,23 @@ PART=${PART:-ab}
 if [[ $PART == *a* ]]; then
 timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > "$OUT/pytest_gpu.log" 2>&1 || exit 1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit 1
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
-timeout -k 10 300 python bench.py --config recovery > "$OUT/recovery.json" 2> "$OUT/recovery.err" || exit 1
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 300 python bench.py --full --config recovery > "$OUT/recovery.json" 2> "$OUT/recovery.err" || exit 1
 for sz in 0 100 1024 4096; do
-  timeout -k 10 200 python bench.py --config entries --entry-size $sz > "$OUT/c3_$sz.json" 2> "$OUT/c3_$sz.err" || exit 1
+  timeout -k 10 200 python bench.py --full --config entries --entry-size $sz > "$OUT/c3_$sz.json" 2> "$OUT/c3_$sz.err" || exit 1
 done
-timeout -k 10 200 python bench.py --config append > "$OUT/append.json" 2> "$OUT/append.err" || exit 1
-timeout -k 10 300 python bench.py --config stream > "$OUT/stream.json" 2> "$OUT/stream.err" || exit 1
+timeout -k 10 200 python bench.py --full --config append > "$OUT/append.json" 2> "$OUT/append.err" || exit 1
+timeout -k 10 300 python bench.py --full --config stream > "$OUT/stream.json" 2> "$OUT/stream.err" || exit 1
 fi
 if [[ $PART == *b* ]]; then
 for v in 64 128 256 512 1024 2048 3072 4096 8192; do
-  timeout -k 10 200 python bench.py --config replay --value-len $v > "$OUT/replay_$v.json" 2> "$OUT/replay_$v.err" || exit 1
+  timeout -k 10 200 python bench.py --full --config replay --value-len $v > "$OUT/replay_$v.json" 2> "$OUT/replay_$v.err" || exit 1
 done
-timeout -k 10 200 python bench.py --config replay > "$OUT/replay.json" 2> "$OUT/replay.err" || exit 1
+timeout -k 10 200 python bench.py --full --config replay > "$OUT/replay.json" 2> "$OUT/replay.err" || exit 1
 # the reference's concurrency shape (RecoverSegmentBenchmark's replay threads)
 for K in ${KS:-1 4 16}; do
-  timeout -k 10 300 python bench.py --config entries --contexts $K > "$OUT/ctx_entries_k$K.json" 2> "$OUT/ctx_entries_k$K.err" || exit 1
-  timeout -k 10 300 python bench.py --config replay --value-len 64 --contexts $K --steps 10 > "$OUT/ctx_replay64_k$K.json" 2> "$OUT/ctx_replay64_k$K.err" || exit 1
+  timeout -k 10 300 python bench.py --full --config entries --contexts $K > "$OUT/ctx_entries_k$K.json" 2> "$OUT/ctx_entries_k$K.err" || exit 1
+  timeout -k 10 300 python bench.py --full --config replay --value-len 64 --contexts $K --steps 10 > "$OUT/ctx_replay64_k$K.json" 2> "$OUT/ctx_replay64_k$K.err" || exit 1
 done
 P="rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof"
 timeout -k 10 200 $P -o c2 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/prof_c2.json" 2> "$OUT/prof_c2.err" || exit 1

@@ -7,7 +7,7 @@ export PYTHONUNBUFFERED=1
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
 tail -2 $O/pytest_gpu.log
-timeout -k 10 300 python bench.py --config recovery --steps 10 --warmup 2 > $O/recovery.json 2> $O/recovery.err || exit 1
+timeout -k 10 300 python bench.py --full --config recovery --steps 10 --warmup 2 > $O/recovery.json 2> $O/recovery.err || exit 1
 cat $O/recovery.json | cut -c1-400
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in base bo0; do

@@ -10,8 +10,8 @@ if [ "${SUITE:-0}" = 1 ]; then
   timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > "$OUT/pytest_gpu.log" 2>&1 || exit 1
 fi
 for K in ${KS:-1 2 4 8 16}; do
-  timeout -k 10 300 python bench.py --config entries --contexts $K --steps ${STEPS:-20} > "$OUT/entries_k$K.json" 2> "$OUT/entries_k$K.err" || exit 1
+  timeout -k 10 300 python bench.py --full --config entries --contexts $K --steps ${STEPS:-20} > "$OUT/entries_k$K.json" 2> "$OUT/entries_k$K.err" || exit 1
   for v in ${VALUES:-64 1024}; do
-    timeout -k 10 300 python bench.py --config replay --value-len $v --contexts $K --steps ${RSTEPS:-10} > "$OUT/replay${v}_k$K.json" 2> "$OUT/replay${v}_k$K.err" || exit 1
+    timeout -k 10 300 python bench.py --full --config replay --value-len $v --contexts $K --steps ${RSTEPS:-10} > "$OUT/replay${v}_k$K.json" 2> "$OUT/replay${v}_k$K.err" || exit 1
   done
 done

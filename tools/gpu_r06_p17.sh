@@ -10,4 +10,4 @@ timeout -k 10 300 python -u -m pytest -x -v --timeout 120 --timeout-method threa
     -m gpu > $O/pytest.log 2>&1 || exit 1
 VARIANTS="p17" CASES="--config replay --value-len 1024;--config replay --value-len 2048;--config replay --value-len 4096;--config replay --value-len 1536;--config replay --value-len 2560" \
   REPS=2 STEPS=10 TAG=r06/${1:-p17}/ab bash tools/gpu_ab.sh || exit 1
-timeout -k 10 200 python bench.py --config replay --value-len 2048 > $O/replay_2048.json 2> $O/replay_2048.err || exit 1
+timeout -k 10 200 python bench.py --full --config replay --value-len 2048 > $O/replay_2048.json 2> $O/replay_2048.err || exit 1
