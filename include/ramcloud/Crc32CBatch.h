@@ -151,6 +151,36 @@ class Crc32CBatch {
     }
 
     /**
+     * The append loop of RecoverySegmentBuilder::build
+     * (src/RecoverySegmentBuilder.cc:61-203) for the replicas a
+     * deviceReplayVerify (or a walk) left in HBM: placement {record,
+     * partition} appends that record of d_entries to recovery segment
+     * (record's segment) * partitions + partition, which lies at d_out + that
+     * index * outStride and holds outCapacity bytes.  d_outCerts gets every
+     * recovery segment's certificate (Segment::getAppendedLength,
+     * src/Segment.cc:672-684) and d_outStatus its flags and entry count: see
+     * ramcrc_recovery_append_device.  The placement list must not decrease in
+     * `record`.  Returns after the kernels finished on `stream`; throws when
+     * the list was refused (nothing is written then).
+     */
+    void
+    deviceRecoveryAppend(const void* d_base, uint64_t stride, uint64_t count,
+                         const ramcrc_seg_status* d_status, const ramcrc_seg_entry* d_entries,
+                         uint64_t entriesCap, const uint64_t* d_nEntries,
+                         const ramcrc_placement* d_place, uint64_t placeCap,
+                         const uint64_t* d_nPlace, uint32_t partitions, void* d_out,
+                         uint64_t outStride, uint32_t outCapacity, ramcrc_seg_cert* d_outCerts,
+                         ramcrc_append_status* d_outStatus, void* stream = NULL)
+    {
+        check(ramcrc_recovery_append_device(context(), d_base, stride, count, d_status, d_entries,
+                                            entriesCap, d_nEntries, d_place, placeCap, d_nPlace,
+                                            partitions, d_out, outStride, outCapacity, d_outCerts,
+                                            d_outStatus, stream),
+              "ramcrc_recovery_append_device");
+        sync(stream);
+    }
+
+    /**
      * Object::assembleForLog's checksum for a batch of serialized objects
      * (the write path, src/ObjectManager.cc:1274): header.checksum of every
      * object (Object::Header + keysAndValue, src/Object.h:137-182) is set to

@@ -38,7 +38,8 @@ enum {
     RAMCRC_EHIP = -3,     /* a HIP runtime call failed; see ramcrc_last_hip_error */
     RAMCRC_ENODEV = -4,   /* no usable gfx950 device */
     RAMCRC_ERCCL = -5,    /* RCCL failure or RCCL unavailable (multi-GPU shard) */
-    RAMCRC_EREFUSED = -6, /* a launch found more chunks than the context's scratch holds and
+    RAMCRC_EREFUSED = -6, /* a launch found more chunks than the context's scratch holds, or
+                             ramcrc_recovery_append_device a placement list it refuses, and
                              wrote none of its outputs (see ramcrc_ctx_check) */
     RAMCRC_EINTERNAL = -7, /* a small-entry launch found its bin layout inconsistent with the
                              entries it binned and wrote none of its small-entry outputs.
@@ -204,7 +205,11 @@ typedef struct ramcrc_seg_status {
  * (about 64 entries per part, 64 KiB .. 1 MiB, chosen per batch on the device from
  * the entry density; see RAMCRC_OPT_SERIAL_WALK, RAMCRC_OPT_WALK_PART_SHIFT).  Writes d_status[i] and one
  * ramcrc_seg_entry per complete entry to d_entries (up to entries_cap; the
- * order across segments is unspecified, within a segment it is increasing).  *d_n_entries (device) receives the
+ * order across segments is unspecified, within a segment it is increasing).
+ * The records of one segment are contiguous in the table: segment s owns one
+ * run of slots, so a list of record indices that does not decrease visits
+ * every segment's records as one run, in offset order
+ * (ramcrc_recovery_append_device relies on it).  *d_n_entries (device) receives the
  * number of entries walked (may exceed entries_cap: see TABLE_FULL).
  * d_base 16-byte aligned, seg_stride a multiple of 16.  Stream-ordered. */
 int ramcrc_segment_walk_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
@@ -229,6 +234,85 @@ int ramcrc_segment_walk_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg
 int ramcrc_segments_certify_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
                                    uint32_t seg_capacity, uint64_t n_seg, const uint32_t* d_heads,
                                    ramcrc_seg_cert* d_certs, uint32_t* d_flags, void* stream);
+
+/* Recovery segments built from walked records: the append loop of
+ * RecoverySegmentBuilder::build (src/RecoverySegmentBuilder.cc:61-203) with
+ * the placement decision (key hash, tablet lookup) left to the caller.  A
+ * placement {record, partition} appends record `record` of the walk table to
+ * the recovery segment of `partition` that belongs to the record's source
+ * segment; a record may be placed any number of times (the reference places
+ * SAFEVERSION and TXPLIST entries in every partition). */
+typedef struct ramcrc_placement {
+    uint32_t record;     /* index into the walk's record table */
+    uint32_t partition;  /* < n_part */
+} ramcrc_placement;
+
+typedef struct ramcrc_append_status {
+    uint32_t flags;    /* RAMCRC_SEG_OK, RAMCRC_SEG_APPEND_FULL or RAMCRC_SEG_SOURCE_BAD */
+    uint32_t entries;  /* entries appended */
+} ramcrc_append_status;
+
+#define RAMCRC_SEG_APPEND_FULL 64u   /* a placement did not fit (Segment::hasSpaceFor,
+                                        src/Segment.cc:136-154, where the reference throws): it
+                                        and every later placement of this output were left out */
+#define RAMCRC_SEG_SOURCE_BAD 128u   /* the source segment's status lacks RAMCRC_SEG_OK: nothing
+                                        appended (build throws before its loop) */
+
+/* There are n_seg * n_part outputs; output k = s * n_part + p lies at d_out +
+ * k * out_stride, holds out_capacity bytes and starts empty (head 0, the
+ * running checksum of a fresh Crc32C).  It receives, in list order, every
+ * placement {record, p} whose record belongs to source segment s, each as
+ * Segment::append(type, payload, length) writes it (src/Segment.cc:197-228):
+ * the header byte type | (lengthBytes - 1) << 6 with the minimal lengthBytes
+ * for `length` (the EntryHeader constructor, src/Segment.h:134-149 -- not
+ * copied from the source header), the length little-endian, the payload.  An
+ * append with head + 1 + lengthBytes + length > out_capacity is refused, and
+ * so is every later one of that output (RAMCRC_SEG_APPEND_FULL); a record
+ * flagged RAMCRC_SEG_ENTRY_OVERLONG never fits.  Outputs of a source segment
+ * without RAMCRC_SEG_OK stay empty (RAMCRC_SEG_SOURCE_BAD).
+ *
+ * d_out_certs[k] = {head, checksum} is Segment::getAppendedLength's
+ * certificate (src/Segment.cc:672-684) of output k, computed from the
+ * placement sizes in the same pass (the outputs are not read back; it equals
+ * what ramcrc_segments_certify_device returns for them); d_out_status[k] =
+ * {flags, entries appended}.  Bytes of an output at or past its head are
+ * never written.
+ *
+ * The list (d_place, *d_n_place entries on the device, at most place_cap)
+ * must not decrease in `record`; with the walk's table order every output
+ * then receives its entries in source-offset order, as build appends them.
+ * The call refuses -- none of d_out, d_out_certs, d_out_status is written and
+ * ramcrc_ctx_check returns RAMCRC_EREFUSED -- when the list decreases, names
+ * a record at or beyond min(*d_n_entries, entries_cap) or a partition >=
+ * n_part, when *d_n_place > place_cap, or when the table's segments are not
+ * contiguous runs.
+ *
+ * d_base 16-byte aligned, seg_stride a multiple of 16 (the walk's rules);
+ * d_out and out_stride are free; n_part > 0; out_stride >= out_capacity;
+ * place_cap < 2^32; the output range must not overlap the source range.
+ * Scratch comes from the context: after ramcrc_ctx_reserve(ctx, 16 + 4 *
+ * n_seg + (n_part > 512 ? 4 * n_seg * n_part : 0), place_cap / 2 + 1), or
+ * after one call of the same shape, it does not allocate.  Stream-ordered,
+ * asynchronous. */
+int ramcrc_recovery_append_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
+                                  uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                  const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                  const uint64_t* d_n_entries, const ramcrc_placement* d_place,
+                                  uint64_t place_cap, const uint64_t* d_n_place, uint32_t n_part,
+                                  void* d_out, uint64_t out_stride, uint32_t out_capacity,
+                                  ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
+                                  void* stream);
+
+/* The same on the host, single-threaded, for a backup without a GPU: host
+ * pointers, n_entries records in `entries`, n_place placements in `place`.
+ * Returns RAMCRC_EINVAL where the device form refuses (nothing is written).
+ * No alignment rules. */
+int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                                const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                                uint64_t n_entries, const ramcrc_placement* place, uint64_t n_place,
+                                uint32_t n_part, void* out, uint64_t out_stride,
+                                uint32_t out_capacity, ramcrc_seg_cert* out_certs,
+                                ramcrc_append_status* out_status);
 
 /* ObjectManager::replaySegment's checksum checks for every record of a walk
  * whose segment passed the metadata check (d_status flags RAMCRC_SEG_OK;
@@ -500,7 +584,8 @@ int ramcrc_ctx_status(ramcrc_ctx* ctx, uint32_t* status);
  * needs a general batch whose buffers
  * overlap or total more bytes than the device holds (ramcrc_batch_device,
  * ramcrc_verify_objects_device, ramcrc_assemble_objects_device); raise
- * ramcrc_ctx_reserve and retry.  The host entry points (ramcrc_batch_host,
+ * ramcrc_ctx_reserve and retry.  ramcrc_recovery_append_device refuses a
+ * placement list that breaks its rules: correct the list.  The host entry points (ramcrc_batch_host,
  * ramcrc_assemble_objects_host) check by themselves. */
 int ramcrc_ctx_check(ramcrc_ctx* ctx, void* stream);
 

@@ -23,7 +23,8 @@ SOURCES = ["ramcrc_device.hip", "ramcrc_host.cc", "ramcrc_shard.hip", "ramcrc_fi
 HEADERS = ["gf2.h", "walk_rules.h", "shard_plan.h",
            # parts of ramcrc_device.hip (one translation unit)
            "dev_common.inc", "dev_chunks.inc", "dev_bins.inc", "dev_entries.inc",
-           "dev_plan.inc", "dev_host.inc", "dev_walk.inc", "dev_checks.inc"]
+           "dev_plan.inc", "dev_host.inc", "dev_walk.inc", "dev_checks.inc",
+           "dev_append.inc"]
 
 
 def hipcc():

@@ -39,6 +39,8 @@
 //    (entry, chunk) with two binary searches.
 //  * k_seg_walk / k_walk_* -- Segment::checkMetadataIntegrity over whole
 //    segments, and the records the replay checks read.
+//  * k_app_* -- walked records appended into per-partition recovery segments,
+//    with their certificates.
 //
 // The kernels live in per-family parts included below, in this order, into
 // this one translation unit (shared __device__ tables and LDS layouts, no
@@ -51,6 +53,7 @@
 //   dev_host.inc     ramcrc_ctx and the host launch helpers
 //   dev_walk.inc     k_seg_walk and the parallel walk (k_walk_*)
 //   dev_checks.inc   k_obj_compare, k_obj_stamp, certificate kernels
+//   dev_append.inc   k_app_mark, k_app_scan, k_app_copy (recovery-segment append)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -84,6 +87,7 @@ using ramcrc::OpTable;
 #include "dev_host.inc"
 #include "dev_walk.inc"
 #include "dev_checks.inc"
+#include "dev_append.inc"
 
 extern "C" {
 
@@ -106,7 +110,7 @@ const char* ramcrc_strerror(int code)
     case RAMCRC_EHIP: return hipGetErrorString(hipError_t(t_last_hip));
     case RAMCRC_ENODEV: return "no usable device";
     case RAMCRC_ERCCL: return "rccl failure";
-    case RAMCRC_EREFUSED: return "launch refused: chunk scratch too small (ramcrc_ctx_reserve)";
+    case RAMCRC_EREFUSED: return "launch refused: chunk scratch too small (ramcrc_ctx_reserve), or a placement list refused";
     case RAMCRC_EINTERNAL: return "launch refused: inconsistent small-entry bin layout";
     case RAMCRC_EPEER: return "another rank of the shard failed this step";
     default: return "unknown error";
@@ -911,6 +915,96 @@ int ramcrc_segments_certify_device(ramcrc_ctx* c, const void* d_base, uint64_t s
         return rc;
     hipLaunchKernelGGL(k_cert_emit, grid, dim3(256), 0, s, tmp, st, d_certs, d_flags, n_seg);
     HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
+                                  uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                  const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                  const uint64_t* d_n_entries, const ramcrc_placement* d_place,
+                                  uint64_t place_cap, const uint64_t* d_n_place, uint32_t n_part,
+                                  void* d_out, uint64_t out_stride, uint32_t out_capacity,
+                                  ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
+                                  void* stream)
+{
+    if (!c || n_part == 0 || out_stride < out_capacity || n_seg > 0xFFFFFFFFull ||
+        place_cap > 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (n_seg == 0)
+        return RAMCRC_OK;
+    if (!d_base || !d_status || !d_n_entries || !d_n_place || !d_out || !d_out_certs ||
+        !d_out_status || (entries_cap && !d_entries) || (place_cap && !d_place))
+        return RAMCRC_EINVAL;
+    const uint64_t B = reinterpret_cast<uint64_t>(d_base), O = reinterpret_cast<uint64_t>(d_out);
+    if ((B & 15) || (seg_stride & 15))
+        return RAMCRC_EINVAL;
+    const uint64_t n_out = n_seg * n_part;   // both below 2^32
+    if ((seg_stride && n_seg > UINT64_MAX / seg_stride) ||
+        (out_stride && n_out > UINT64_MAX / out_stride) || n_out > UINT64_MAX / sizeof(AppState))
+        return RAMCRC_EINVAL;
+    const uint64_t src_bytes = n_seg * seg_stride, out_bytes = n_out * out_stride;
+    if (B > UINT64_MAX - src_bytes || O > UINT64_MAX - out_bytes ||
+        (B < O + out_bytes && O < B + src_bytes))
+        return RAMCRC_EINVAL;   // the outputs would overwrite the source
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch words in the chunk-partial buffer: the refusal word, the
+    // segments' runs, then the scan states when they do not fit in LDS; the
+    // placements' offsets in the plan buffer (ramcrc.h states these sizes)
+    const uint64_t head_words = (4 + 3 * n_seg + 3) & ~uint64_t(3);
+    const uint64_t state_words = n_part > kAppLdsParts ? n_out * (sizeof(AppState) / 4) : 0;
+    int rc = reserve_locked(c, head_words + state_words, place_cap / 2 + 1);
+    if (rc)
+        return rc;
+    AppDesc a{};
+    a.base = B;
+    a.stride = seg_stride;
+    a.nseg = n_seg;
+    a.status = d_status;
+    a.entries = reinterpret_cast<const u32x4*>(d_entries);
+    a.ecap = entries_cap;
+    a.n_entries = d_n_entries;
+    a.place = reinterpret_cast<const uint2*>(d_place);
+    a.pcap = place_cap;
+    a.n_place = d_n_place;
+    a.npart = n_part;
+    a.ocap = out_capacity;
+    a.out = O;
+    a.ostride = out_stride;
+    a.certs = d_out_certs;
+    a.ostat = d_out_status;
+    a.refuse = c->partials;
+    a.run_lo = c->partials + 4;
+    a.run_hi = a.run_lo + n_seg;
+    a.run_cnt = a.run_hi + n_seg;
+    a.pdst = reinterpret_cast<uint32_t*>(c->plan_local);
+    a.states = reinterpret_cast<AppState*>(c->partials + head_words);
+    a.ctx_status = c->status;
+    HIPCHK(hipMemsetAsync(c->partials, 0, head_words * sizeof(uint32_t), s));
+    const uint64_t cap_grid = uint64_t(8) * c->ncu;
+    uint64_t gm = (place_cap + 255) / 256;
+    gm = gm < 1 ? 1 : (gm > cap_grid ? cap_grid : gm);
+    hipLaunchKernelGGL(k_app_mark, dim3(uint32_t(gm)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    // waves per source segment: about 16 waves per CU in all, at most 8 and
+    // no more than there are partitions
+    uint32_t nown = 1;
+    while (nown < 8 && 2 * nown <= n_part && n_seg * (2 * nown) <= uint64_t(16) * c->ncu)
+        nown *= 2;
+    a.nown = nown;
+    const uint64_t gs = n_seg * nown < uint64_t(16) * c->ncu ? n_seg * nown : uint64_t(16) * c->ncu;
+    if (n_part <= kAppLdsParts)
+        hipLaunchKernelGGL(k_app_scan<true>, dim3(uint32_t(gs)), dim3(kWaveSize), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_app_scan<false>, dim3(uint32_t(gs)), dim3(kWaveSize), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (place_cap) {
+        uint64_t gc = (place_cap + kAppCopyThreads - 1) / kAppCopyThreads;
+        gc = gc > cap_grid ? cap_grid : gc;
+        hipLaunchKernelGGL(k_app_copy, dim3(uint32_t(gc)), dim3(kAppCopyThreads), 0, s, a);
+        HIPCHK(hipGetLastError());
+    }
     return RAMCRC_OK;
 }
 

@@ -214,4 +214,77 @@ int ramcrc_segment_fill_objects(uint8_t* seg, uint32_t capacity, uint32_t value_
     return RAMCRC_OK;
 }
 
+// The append loop of RecoverySegmentBuilder::build
+// (src/RecoverySegmentBuilder.cc:61-203) over a caller's placement list: one
+// Segment::append (src/Segment.cc:197-228) per placement, into the recovery
+// segment (source segment, partition), while hasSpaceFor (:136-154) holds.
+// Two passes over the list: the first checks it, so a refused call writes
+// nothing.
+int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                                const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                                uint64_t n_entries, const ramcrc_placement* place, uint64_t n_place,
+                                uint32_t n_part, void* out, uint64_t out_stride,
+                                uint32_t out_capacity, ramcrc_seg_cert* out_certs,
+                                ramcrc_append_status* out_status)
+{
+    if (n_part == 0 || out_stride < out_capacity || n_seg > 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (n_seg == 0)
+        return RAMCRC_OK;
+    if (!base || !status || !out || !out_certs || !out_status || (n_entries && !entries) ||
+        (n_place && !place))
+        return RAMCRC_EINVAL;
+    const uint64_t n_out = n_seg * n_part;   // < 2^64: both below 2^32
+    if ((seg_stride && n_seg > UINT64_MAX / seg_stride) ||
+        (out_stride && n_out > UINT64_MAX / out_stride))
+        return RAMCRC_EINVAL;
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(base), ob = reinterpret_cast<uintptr_t>(out);
+    const uint64_t src_bytes = n_seg * seg_stride, out_bytes = n_out * out_stride;
+    if (sb < ob + out_bytes && ob < sb + src_bytes)
+        return RAMCRC_EINVAL;   // the outputs would overwrite the source
+    for (uint64_t i = 0; i < n_place; i++) {
+        if (place[i].record >= n_entries || place[i].partition >= n_part ||
+            (i && place[i].record < place[i - 1].record) ||
+            entries[place[i].record].segment >= n_seg)
+            return RAMCRC_EINVAL;
+    }
+    uint8_t* const o = static_cast<uint8_t*>(out);
+    for (uint64_t k = 0; k < n_out; k++) {
+        // head 0, a fresh Crc32C; the running state is kept in the certificate
+        out_certs[k] = ramcrc_seg_cert{0u, 0xFFFFFFFFu};
+        out_status[k] = ramcrc_append_status{
+            (status[k / n_part].flags & RAMCRC_SEG_OK) ? RAMCRC_SEG_OK : RAMCRC_SEG_SOURCE_BAD, 0u};
+    }
+    for (uint64_t i = 0; i < n_place; i++) {
+        const ramcrc_seg_entry& r = entries[place[i].record];
+        const uint64_t k = uint64_t(r.segment) * n_part + place[i].partition;
+        if (out_status[k].flags != RAMCRC_SEG_OK)
+            continue;   // bad source, or full: nothing more is appended
+        const uint32_t len = r.length;
+        const uint32_t lb = len < 0x100u ? 1 : len < 0x10000u ? 2 : len < 0x1000000u ? 3 : 4;
+        const uint64_t src = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+        const uint32_t head = out_certs[k].segment_length;
+        if ((r.header & RAMCRC_SEG_ENTRY_OVERLONG) || src + len > seg_stride ||
+            uint64_t(head) + 1 + lb + len > out_capacity) {
+            out_status[k].flags = RAMCRC_SEG_APPEND_FULL;
+            continue;
+        }
+        uint8_t* e = o + k * out_stride + head;
+        e[0] = uint8_t((r.header & 0x3f) | ((lb - 1) << 6));
+        for (uint32_t b = 0; b < lb; b++)
+            e[1 + b] = uint8_t(len >> (8 * b));
+        out_certs[k].checksum = ramcrc_update(out_certs[k].checksum, e, 1 + lb);
+        memcpy(e + 1 + lb, static_cast<const uint8_t*>(base) + r.segment * seg_stride + src, len);
+        out_certs[k].segment_length = head + 1 + lb + len;
+        out_status[k].entries++;
+    }
+    for (uint64_t k = 0; k < n_out; k++) {
+        uint8_t lenle[4];
+        for (int b = 0; b < 4; b++)
+            lenle[b] = uint8_t(out_certs[k].segment_length >> (8 * b));
+        out_certs[k].checksum = ~ramcrc_update(out_certs[k].checksum, lenle, 4);
+    }
+    return RAMCRC_OK;
+}
+
 }  // extern "C"

@@ -20,11 +20,13 @@ _lib = None
 FINALIZE = 1
 
 _ERRORS = {0: "ok", -1: "invalid argument", -2: "out of memory", -3: "HIP error",
-           -4: "no usable device", -5: "RCCL error", -6: "launch refused (scratch too small)",
+           -4: "no usable device", -5: "RCCL error", -6: "launch refused (scratch too small, or a placement list refused)",
            -7: "launch refused (inconsistent bin layout)",
            -8: "another shard rank failed"}
 
+EINVAL = -1
 ENOMEM = -2
+EREFUSED = -6
 EINTERNAL = -7
 EPEER = -8
 
@@ -86,6 +88,10 @@ def lib():
         "ramcrc_verify_objects_device": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
         "ramcrc_replay_verify_device": (i32, [vp, vp, u64, u32, u64, vp, vp, vp, u64, vp, vp, vp]),
         "ramcrc_segments_certify_device": (i32, [vp, vp, u64, u32, u64, vp, vp, vp, vp]),
+        "ramcrc_recovery_append_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u64, vp, u32,
+                                                vp, u64, u32, vp, vp, vp]),
+        "ramcrc_recovery_append_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u64, u32, vp, u64, u32,
+                                              vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -218,6 +224,38 @@ def segment_fill_objects(seg, value_len, first_key=0):
                                            first_key, _c.byref(n), _c.c_void_p(cert.ctypes.data))
     _check(rc, "ramcrc_segment_fill_objects")
     return n.value, int(cert[0]), int(cert[1])
+
+
+def recovery_append_host(segments, seg_stride, n_seg, status, entries, place, n_part, out,
+                         out_stride, out_capacity):
+    """RecoverySegmentBuilder::build's append loop on the host
+    (ramcrc_recovery_append_host).  All arguments are C-contiguous numpy
+    arrays: segments uint8; status uint32 [n_seg, 4]; entries uint32 [n, 4]
+    (segment, offset, length, header); place uint32 [m, 2] (record,
+    partition) or segments.PLACEMENT_DTYPE [m]; out uint8, written in place.
+    Returns (certs uint32 [n_seg * n_part, 2], status uint32 [n_seg * n_part,
+    2]); raises RamcrcError (code EINVAL) where the device form refuses."""
+    def arr(a, dtype):
+        a = np.asarray(a)
+        if a.dtype.fields is not None:
+            a = a.view(np.uint32)
+        if a.dtype != dtype or not a.flags.c_contiguous:
+            raise RamcrcError(f"expected a contiguous {np.dtype(dtype).name} array")
+        return a
+    segments, out = arr(segments, np.uint8), arr(out, np.uint8)
+    status, entries, place = arr(status, np.uint32), arr(entries, np.uint32), arr(place, np.uint32)
+    n_out = int(n_seg) * int(n_part)
+    if (segments.size < n_seg * seg_stride or out.size < n_out * out_stride
+            or status.size < 4 * n_seg or not out.flags.writeable):
+        raise RamcrcError("recovery_append_host: an array is smaller than its geometry")
+    certs = np.zeros((n_out, 2), np.uint32)
+    ostat = np.zeros((n_out, 2), np.uint32)
+    p = lambda a: _c.c_void_p(a.ctypes.data)
+    rc = lib().ramcrc_recovery_append_host(p(segments), seg_stride, n_seg, p(status), p(entries),
+                                           entries.size // 4, p(place), place.size // 2, n_part,
+                                           p(out), out_stride, out_capacity, p(certs), p(ostat))
+    _check(rc, "ramcrc_recovery_append_host")
+    return certs, ostat
 
 
 # ---------------------------------------------------------------- device
@@ -391,6 +429,23 @@ class Context:
                                                   _stream(stream))
         _check(rc, "ramcrc_segments_certify_device")
         return certs
+
+    def recovery_append(self, data, seg_stride, nseg, status, entries, n_entries, place, n_place,
+                        n_part, out, out_stride, out_capacity, out_certs, out_status, stream=None):
+        """Append walked records into per-partition recovery segments and seal
+        them (ramcrc_recovery_append_device).  status, entries, n_entries: a
+        walk's tables; place: int32 CUDA [cap, 2] (record, partition), not
+        decreasing in record; n_place: int64 CUDA [1]; out: uint8 CUDA holding
+        nseg * n_part outputs at out_stride; out_certs, out_status: int32 CUDA
+        [nseg * n_part, 2].  Asynchronous; a refused list shows in check()."""
+        ecap = 0 if entries is None else entries.shape[0]
+        pcap = 0 if place is None else place.shape[0]
+        rc = lib().ramcrc_recovery_append_device(
+            self._h, _ptr(data), seg_stride, nseg, _ptr(status), _ptr(entries), ecap,
+            _ptr(n_entries), _ptr(place), pcap, _ptr(n_place), n_part, _ptr(out), out_stride,
+            out_capacity, _ptr(out_certs), _ptr(out_status), _stream(stream))
+        _check(rc, "ramcrc_recovery_append_device")
+        return out_certs
 
     def verify_objects(self, data, seg_stride, entries, n_entries, obj_crc, status, stream=None):
         """Object::computeChecksum + comparison for every object record of a walk."""

@@ -28,6 +28,11 @@ SEG_PAST_LENGTH = 4
 SEG_BAD_CHECKSUM = 8
 SEG_TABLE_FULL = 16
 SEG_CYCLE = 32
+SEG_APPEND_FULL = 64    # ramcrc_append_status.flags: a placement did not fit
+SEG_SOURCE_BAD = 128    # ramcrc_append_status.flags: the source segment failed its check
+# ramcrc_placement, ramcrc_append_status, and the records and certificates they go with
+PLACEMENT_DTYPE = np.dtype([("record", "<u4"), ("partition", "<u4")])
+APPEND_STATUS_DTYPE = np.dtype([("flags", "<u4"), ("entries", "<u4")])
 LOG_ENTRY_TYPE_OBJ = 2          # src/LogEntryTypes.h:35
 LOG_ENTRY_TYPE_OBJTOMB = 3      # src/LogEntryTypes.h:38
 LOG_ENTRY_TYPE_SAFEVERSION = 5  # src/LogEntryTypes.h:44

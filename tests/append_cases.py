@@ -1,0 +1,209 @@
+"""Sources, placement lists and the independent expectation for the recovery
+append tests (ramcrc_recovery_append_host / _device).
+
+The expectation restates Segment::append (src/Segment.cc:197-228) in plain
+Python over the record table and the source bytes: header byte with the
+minimal length bytes (src/Segment.h:134-149), the length little-endian, the
+payload; refused once head + 1 + lengthBytes + length exceeds the capacity
+(src/Segment.cc:136-154).  The expected certificate is the oracle's
+checkMetadataIntegrity restatement over the expected bytes.
+"""
+import numpy as np
+
+from ramcloud_amd import segments
+
+import segment_cases
+
+KiB = 1024
+FILL = 0xA5
+
+
+def len_bytes(n):
+    return 1 if n < 1 << 8 else 2 if n < 1 << 16 else 3 if n < 1 << 24 else 4
+
+
+def raw_entry(etype, payload, length_bytes=None):
+    """An entry as it may sit in a source: length_bytes may exceed the minimum."""
+    n = len(payload)
+    lb = len_bytes(n) if length_bytes is None else length_bytes
+    return bytes([etype | ((lb - 1) << 6)]) + n.to_bytes(lb, "little") + payload
+
+
+def source_of(oracle, entry_lists, cap):
+    """One segment of `cap` bytes per list of entries; certificates from the oracle."""
+    nseg = len(entry_lists)
+    buf = np.zeros(nseg * cap, np.uint8)
+    certs = np.zeros((nseg, 2), np.uint32)
+    for i, es in enumerate(entry_lists):
+        blob = b"".join(es)
+        assert len(blob) <= cap
+        buf[i * cap:i * cap + len(blob)] = np.frombuffer(blob, np.uint8)
+        _, ck, _, _ = oracle.check_metadata(buf[i * cap:(i + 1) * cap], len(blob), 0)
+        certs[i] = (len(blob), ck)
+    return buf, certs
+
+
+def host_walk(oracle, buf, certs, nseg, cap):
+    """(status uint32 [nseg, 4], table uint32 [n, 4]) from the oracle's walk."""
+    status = np.zeros((nseg, 4), np.uint32)
+    tables = [np.zeros((0, 4), np.uint32)]
+    for i in range(nseg):
+        f, ck, n, t = oracle.check_metadata(buf[i * cap:(i + 1) * cap], int(certs[i, 0]),
+                                            int(certs[i, 1]), segment=i, capacity=cap,
+                                            table_cap=cap + 1)
+        status[i, :3] = (f, ck, n)
+        tables.append(t)
+    return status, np.ascontiguousarray(np.concatenate(tables))
+
+
+def expected(src, stride, table, status, place, n_seg, n_part, cap):
+    """(bytes per output, flags per output, entries per output)."""
+    n_out = n_seg * n_part
+    outs = [bytearray() for _ in range(n_out)]
+    flags = [segments.SEG_OK if int(status[k // n_part, 0]) & segments.SEG_OK
+             else segments.SEG_SOURCE_BAD for k in range(n_out)]
+    counts = [0] * n_out
+    for rec, part in np.asarray(place, np.uint32).reshape(-1, 2).tolist():
+        seg, off, ln, hdr = (int(v) for v in table[rec])
+        k = seg * n_part + part
+        if flags[k] != segments.SEG_OK:
+            continue
+        lb = len_bytes(ln)
+        if (hdr & 0x100) or len(outs[k]) + 1 + lb + ln > cap:
+            flags[k] = segments.SEG_APPEND_FULL
+            continue
+        p = seg * stride + off + 1 + ((hdr >> 6) & 3) + 1
+        outs[k] += bytes([(hdr & 0x3F) | ((lb - 1) << 6)]) + ln.to_bytes(lb, "little")
+        outs[k] += src[p:p + ln].tobytes()
+        counts[k] += 1
+    return outs, flags, counts
+
+
+def expected_cert(oracle, data):
+    """Segment::getAppendedLength's certificate of a segment holding `data`."""
+    head = len(data)
+    seg = np.zeros(max(head, 16), np.uint8)
+    seg[:head] = np.frombuffer(bytes(data), np.uint8)
+    return head, oracle.check_metadata(seg, head, 0)[1]
+
+
+def check_outputs(oracle, exp, out, out_stride, cap, certs, ostat, what=""):
+    outs, flags, counts = exp
+    certs = np.asarray(certs).view(np.uint32).reshape(-1, 2)
+    ostat = np.asarray(ostat).view(np.uint32).reshape(-1, 2)
+    assert certs.shape[0] == len(outs) and ostat.shape[0] == len(outs)
+    for k, data in enumerate(outs):
+        head, ck = expected_cert(oracle, data)
+        region = out[k * out_stride:(k + 1) * out_stride]
+        assert tuple(certs[k]) == (head, ck), (what, k, tuple(certs[k]), (head, ck))
+        assert tuple(ostat[k]) == (flags[k], counts[k]), (what, k, tuple(ostat[k]), flags[k], counts[k])
+        assert region[:head].tobytes() == bytes(data), (what, k, "bytes below the head")
+        assert (region[head:] == FILL).all(), (what, k, "a write at or past the head")
+        # the built segment passes the reference's own check with its certificate
+        seg = np.zeros(max(cap, 16), np.uint8)
+        seg[:head] = region[:head]
+        f, _, n, _ = oracle.check_metadata(seg, head, int(certs[k, 1]))
+        assert f == segments.SEG_OK and n == counts[k], (what, k, f, n)
+
+
+# ------------------------------------------------------------------ cases
+def golden_source(golden):
+    """"hi", "yo!" and an empty source (src/SegmentTest.cc:159, 373, 369); the
+    expected output certificates in the same order."""
+    cap = 64 * KiB
+    gold = {c["segmentLength"]: c for c in golden["segment_certificates"]}
+    order = [gold[4], gold[5], gold[0]]
+    buf = np.zeros(3 * cap, np.uint8)
+    for i, payload in enumerate((b"hi", b"yo!")):
+        e = raw_entry(segments.LOG_ENTRY_TYPE_OBJ, payload)
+        buf[i * cap:i * cap + len(e)] = np.frombuffer(e, np.uint8)
+    certs = np.array([(c["segmentLength"], c["checksum"]) for c in order], np.uint32)
+    return buf, certs, cap
+
+
+def mixed_placements(table, n_part, seed):
+    """About 10 % of the records dropped, about 5 % placed in every partition,
+    some placed twice in one partition, the rest in one seeded partition."""
+    rng = np.random.default_rng(seed)
+    place = []
+    for rec in range(table.shape[0]):
+        u = rng.random()
+        if u < 0.10:
+            continue
+        if u < 0.15:
+            place += [(rec, p) for p in range(n_part)]
+            continue
+        p = int(rng.integers(n_part))
+        place.append((rec, p))
+        if u > 0.95:
+            place.append((rec, p))
+    return np.array(place, np.uint32).reshape(-1, 2)
+
+
+def alignment_source(oracle, cap=256 * KiB, seed=16):
+    """Payload lengths 0 .. 80 at every source alignment."""
+    rng = np.random.default_rng(seed)
+    es, pos = [], 0
+    while True:
+        e = raw_entry(segments.LOG_ENTRY_TYPE_OBJ,
+                      rng.integers(0, 256, int(rng.integers(0, 81)), dtype=np.uint8).tobytes())
+        if pos + len(e) > cap - 64:
+            break
+        es.append(e)
+        pos += len(e)
+    return source_of(oracle, [es], cap)
+
+
+def alignment_placements(table, n_part, seed=17):
+    rng = np.random.default_rng(seed)
+    keep = rng.random(table.shape[0]) < 0.9
+    part = rng.integers(0, n_part, table.shape[0])
+    return np.array([(r, int(part[r])) for r in range(table.shape[0]) if keep[r]],
+                    np.uint32).reshape(-1, 2)
+
+
+def alignment_pairs(table, place, n_part, stride):
+    """The (source payload start mod 16, destination payload start mod 16)
+    pairs a placement list produces (outputs and sources 16-byte aligned)."""
+    heads = {}
+    pairs = set()
+    for rec, part in place.tolist():
+        seg, off, ln, hdr = (int(v) for v in table[rec])
+        k = seg * n_part + part
+        lb = len_bytes(ln)
+        h = heads.get(k, 0)
+        pairs.add(((seg * stride + off + 1 + ((hdr >> 6) & 3) + 1) % 16, (h + 1 + lb) % 16))
+        heads[k] = h + 1 + lb + ln
+    return pairs
+
+
+def boundary_source(oracle, cap=1024 * KiB, seed=18):
+    """Payloads at the length-byte boundaries, and one entry whose source
+    header carries 2 length bytes for a 10-byte payload."""
+    rng = np.random.default_rng(seed)
+    rand = lambda n: rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+    T = segments.LOG_ENTRY_TYPE_OBJ
+    es = [raw_entry(T, rand(255)), raw_entry(T, rand(10), length_bytes=2), raw_entry(T, rand(256)),
+          raw_entry(T, rand(65535)), raw_entry(3, rand(0)), raw_entry(T, rand(65536)),
+          raw_entry(T, rand(33), length_bytes=4), raw_entry(T, rand(1)),
+          # (and the sizes at which the device copy changes its lane groups: 256/257, 2047/2048, 65535/65536)
+          raw_entry(T, rand(2047)), raw_entry(T, rand(2048)), raw_entry(T, rand(257))]
+    return source_of(oracle, [es], cap)
+
+
+def capacity_case(oracle, seed=19):
+    """Output 0 is filled exactly by its last entry; output 1 is one byte
+    short for its third and gets more placements after it."""
+    rng = np.random.default_rng(seed)
+    rand = lambda n: rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+    T = segments.LOG_ENTRY_TYPE_OBJ
+    lens = [100, 300, 50, 51, 0, 7, 20]
+    buf, certs = source_of(oracle, [[raw_entry(T, rand(n)) for n in lens]], 64 * KiB)
+    place = np.array([(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (3, 1), (4, 1), (5, 1), (6, 1)],
+                     np.uint32)
+    out_capacity = (1 + 1 + 100) + (1 + 2 + 300) + (1 + 1 + 50)
+    return buf, certs, 64 * KiB, place, 2, out_capacity
+
+
+def small_mixed(oracle, nseg, seed):
+    return segment_cases.mixed_segments(oracle, nseg, 64 * KiB, seed=seed)[:2]
