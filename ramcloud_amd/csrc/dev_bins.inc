@@ -68,29 +68,11 @@ __device__ __forceinline__ uint32_t replay_hard(uint32_t pos, uint32_t len, uint
     // takes the general loop instead of the two-window ring)
     return steps <= 2 ? 1u : (steps <= uint32_t(kTinyK) ? 5u : kHardAll | 4u);
 }
-#ifndef RAMCRC_ENT_NT
-#define RAMCRC_ENT_NT 1
-#endif
 #ifndef RAMCRC_PU
 #define RAMCRC_PU 2   // A/B on the config-3 mix, 1 KiB and 4 KiB entries: 2 < 1, 3, 4, 6, 8
 #endif
 constexpr int kPU = RAMCRC_PU;             // ping-pong depth (pipelined bins)
-#ifndef RAMCRC_TINY_TRIM
-#define RAMCRC_TINY_TRIM 1   // tiny phase: 64-bit-shift head masks, saturating row bases
-#endif
-#ifndef RAMCRC_TINY_CF
-#define RAMCRC_TINY_CF 1     // tiny phase: conflict-free column-major table (tiny_run_cf)
-#endif
-#ifndef RAMCRC_TINY_SAFE
-#define RAMCRC_TINY_SAFE 1    // tiny_run_cf: unclamped window loads when every window of a q is page-safe
-#endif
-#ifndef RAMCRC_TINY_OVL
-#define RAMCRC_TINY_OVL 1   // tiny phase: round 0's windows in flight while the table is built
-#endif
 constexpr uint32_t kNoIdx = 0xFFFFFFFFu;   // empty slot
-#ifndef RAMCRC_SPLIT
-#define RAMCRC_SPLIT 1   // k_entries: tiny and long phases on separate workgroups when a batch has both
-#endif
 #ifndef RAMCRC_SPLIT_KAPPA
 #define RAMCRC_SPLIT_KAPPA 256   // a tiny window in long-phase work units, x 1024
 #endif
@@ -120,50 +102,15 @@ static_assert(RAMCRC_ENT_WAVES % 4 == 0, "age ranks of four waves");
 #define RAMCRC_BIN_PER 4
 #endif
 constexpr int kBinPer = RAMCRC_BIN_PER;    // entries per thread per tile (count/scatter)
-#ifndef RAMCRC_BIN_ONE
-#define RAMCRC_BIN_ONE 0   // k_bin_one for batches of <= 1 tile per workgroup (RAMCRC_OPT_BIN_ONE):
-                           // off since round 6, the two-launch binning measured equal or faster
-#endif
 #ifndef RAMCRC_BIN_SLICES
 #define RAMCRC_BIN_SLICES 8   // k_bin_one: histogram copies (workgroup i adds to copy i % 8: its XCD's)
 #endif
 constexpr int kBinSlices = RAMCRC_BIN_SLICES;
-#ifndef RAMCRC_COUNT_PF
-#define RAMCRC_COUNT_PF 1   // k_bin_count, records: next tile's records in flight (A/B: 0)
-#endif
 #ifndef RAMCRC_BIN_WGS_PER_CU
 #define RAMCRC_BIN_WGS_PER_CU 8
 #endif
 constexpr uint64_t kBinWgsPerCu = RAMCRC_BIN_WGS_PER_CU;   // binning grid cap per CU
 
-#ifndef RAMCRC_TINY_PF
-// tiny rounds: the next round's windows loaded into registers while this one
-// is hashed -- 0 never, 1 always, 2 records batches only (replay)
-#define RAMCRC_TINY_PF 2
-#endif
-#ifndef RAMCRC_TINY_LSEL
-// tiny windows: per-lane v_perm selectors instead of a v_alignbyte per dword
-// -- 0 never, 1 always, 2 where the round loop has no register prefetch
-#define RAMCRC_TINY_LSEL 2
-#endif
-#ifndef RAMCRC_TINY_DM
-#define RAMCRC_TINY_DM 1   // records batches whose objects all span 2 .. kTinyK windows: no scatter
-#endif
-#ifndef RAMCRC_TINY_M2
-#define RAMCRC_TINY_M2 1   // tiny_multi: bin 2 with two-window buffers and a ring of four
-#endif
-#ifndef RAMCRC_TINY_REGEO
-#define RAMCRC_TINY_REGEO 1   // prefetching tiny loop: window geometry re-swizzled from the owner
-#endif
-#ifndef RAMCRC_TINY_T3
-#define RAMCRC_TINY_T3 1   // tiny windows: tail masks on dword 3 only when every window ends at >= 96
-#endif
-#ifndef RAMCRC_TINY_MED3
-#define RAMCRC_TINY_MED3 1   // tiny window tail clamp as one v_med3 per dword
-#endif
-#ifndef RAMCRC_TINY_HM
-#define RAMCRC_TINY_HM 1   // 8-lane group XOR: third step by DPP row_half_mirror (0: ds_swizzle)
-#endif
 // XOR of the 8 lanes of a lane group (lanes 8g .. 8g + 7), in every lane:
 // quad permutes for lane ^ 1 and ^ 2; then every lane of a quad holds the
 // quad's XOR, and row_half_mirror (lane i of a half-row reads lane 7 - i)
@@ -173,11 +120,7 @@ __device__ __forceinline__ uint32_t group8_xor_all(uint32_t R)
 {
     R ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(R), 0xB1, 0xF, 0xF, false));   // lane ^ 1
     R ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(R), 0x4E, 0xF, 0xF, false));   // lane ^ 2
-#if RAMCRC_TINY_HM
     R ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(R), 0x141, 0xF, 0xF, false));  // row_half_mirror
-#else
-    R ^= uint32_t(__builtin_amdgcn_ds_swizzle(int(R), 0x1F | (4 << 10)));           // lane ^ 4
-#endif
     return R;
 }
 
@@ -390,7 +333,7 @@ __global__ __launch_bounds__(kThreads) void k_bin_count(BatchDesc d, Sorted so, 
     const uint32_t sv = sum ? *sum : 3u;
     if ((sv & kSumFast) && !(sv & kHardFull))
         return;   // verified in the walk (k_walk_copyv, k_left): an empty layout, nothing to scan
-    if (!(sv & 1u) || (RAMCRC_TINY_DM && kTinyK >= 2 && !(sv & 2u))) {
+    if (!(sv & 1u) || (kTinyK >= 2 && !(sv & 2u))) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             ctr.hist[(sv & 1u) ? 2 : 1] = uint32_t(entry_count<kMode>(d));
             ctr.wide = (sv & 4u) ? 1u : 0u;
@@ -411,7 +354,7 @@ __global__ __launch_bounds__(kThreads) void k_bin_count(BatchDesc d, Sorted so, 
     // flight while this tile's segment status words are read and binned.
     // Order per tile: status loads (their records arrived last tile), then the
     // next tile's record loads, then the wait for the status words only.
-    constexpr bool kPf = kMode == kRecords && RAMCRC_COUNT_PF;
+    constexpr bool kPf = kMode == kRecords;
     [[maybe_unused]] u32x4 nr[kBinPer];
     if constexpr (kPf) {
 #pragma unroll
@@ -660,9 +603,9 @@ __global__ __launch_bounds__(kThreads) void k_bin_scatter(BatchDesc d, Sorted so
         cnt[t] = 0;
     __syncthreads();
     if (!bin_layout(so, sc, blockIdx.x == 0,
-                    (kMode == kTable || kMode == kRecords) && RAMCRC_TINY_CF ? entry_count<kMode>(d) : 0,
+                    (kMode == kTable || kMode == kRecords) ? entry_count<kMode>(d) : 0,
                     rescue ? tot : nullptr,
-                    (kMode == kRecords || kMode == kTable) && RAMCRC_TINY_DM && kTinyK >= 2
+                    (kMode == kRecords || kMode == kTable) && kTinyK >= 2
                         ? entry_count<kMode>(d) : 0))
         return;   // corrupted histogram: nothing is scattered, k_entries refuses
     if (sc.direct || sc.multi)
@@ -911,7 +854,7 @@ __global__ __launch_bounds__(kThreads) void k_bin_one(BatchDesc d, Sorted so, in
     // (straggler: test hook, one workgroup more than launched, which never comes)
     if (!grid_arrive(ctr, gridDim.x + straggler))
         return;   // aborted: the guarded scatter bins the batch
-    constexpr bool kDirect = (kMode == kTable || kMode == kRecords) && RAMCRC_TINY_CF;
+    constexpr bool kDirect = kMode == kTable || kMode == kRecords;
     if constexpr (kDirect) {
         // Every entry tiny (the direct path: nothing to scatter)?  Bins 0 and
         // 1 and the inactive count decide it -- 17 loads instead of the 8 x 161
@@ -957,8 +900,8 @@ __global__ __launch_bounds__(kThreads) void k_bin_one(BatchDesc d, Sorted so, in
     }
     __syncthreads();
     const bool ok = bin_layout(so, sc, blockIdx.x == 0,
-                               (kMode == kTable || kMode == kRecords) && RAMCRC_TINY_CF ? n : 0, h,
-                               (kMode == kRecords || kMode == kTable) && RAMCRC_TINY_DM && kTinyK >= 2 ? n : 0);
+                               (kMode == kTable || kMode == kRecords) ? n : 0, h,
+                               (kMode == kRecords || kMode == kTable) && kTinyK >= 2 ? n : 0);
     if (blockIdx.x == 0)   // what k_entries checks: every bin holds what was placed in it
         for (int t = threadIdx.x; t < kNB; t += blockDim.x)
             ctr.cursor[t] = sc.count[t];

@@ -176,18 +176,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_chunks(BatchDesc d, Plan pl, ui
             atomicOr(pl.status, 3u);   // refused: this launch, and sticky until checked
         return;
     }
-    // Work: chunk g -> (buffer i, chunk k).  Dynamic: lane 0 takes tickets
-    // from a device counter (one ahead, so the atomic's latency hides behind
-    // a chunk); static: grid stride.
-    auto take = [&]() -> uint64_t {
-        uint64_t t = 0;
-        if (lane == 0)
-            t = atomicAdd(pl.ticket, 1ull);
-        return rfl64(t);
-    };
-    uint64_t g = kDynamic ? take() : wave;
+    // Work: chunk g -> (buffer i, chunk k), grid stride.
+    uint64_t g = wave;
     while (g < total) {
-        const uint64_t gnext = kDynamic ? take() : g + nwaves;
+        const uint64_t gnext = g + nwaves;
         uint64_t i, k;
         if (kMode == kSegAligned) {
             i = g / per_seg;
@@ -256,8 +248,6 @@ __global__ __launch_bounds__(256) void k_combine(BatchDesc d, Plan pl, uint64_t 
 {
     const int lane = threadIdx.x & (kWaveSize - 1);
     const uint64_t wave = uint64_t(blockIdx.x) * (256 / kWaveSize) + threadIdx.x / kWaveSize;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *pl.ticket = 0;   // k_chunks of this launch is complete (same stream)
     if (kMode != kSegAligned && (plan_empty(pl) || ((*pl.status) & kStatusRefused)))
         return;   // nothing large, or k_chunks refused the launch (partials overflow)
     const uint64_t n = entry_count<kMode>(d);

@@ -16,18 +16,11 @@ constexpr uint32_t kBlock = 1024;                  // bytes per wave step
 #ifndef RAMCRC_UNROLL
 #define RAMCRC_UNROLL 4
 #endif
-#ifndef RAMCRC_ASM_XOR3
-#define RAMCRC_ASM_XOR3 1
-#endif
-#ifndef RAMCRC_DYNAMIC
-#define RAMCRC_DYNAMIC 0
-#endif
 constexpr int kChunkShift = RAMCRC_CHUNK_SHIFT;
 constexpr uint64_t kChunk = 1ull << kChunkShift;   // 256 KiB per wave work item
 constexpr uint64_t kLargeMin = 64 * 1024;          // batch API threshold
 constexpr uint64_t kWideCombineMin = 16384;        // tables above: k_combine<kWide>
 constexpr int kUnroll = RAMCRC_UNROLL;             // blocks per register group (x2 in flight)
-constexpr bool kDynamic = RAMCRC_DYNAMIC;          // waves dequeue chunks from a counter
 
 // ------------------------------------------------------------------ tables
 struct alignas(16) DeviceTables {
@@ -38,13 +31,9 @@ struct alignas(16) DeviceTables {
     uint32_t xblk[4][256];  // x^(8 * 1024 * b * 256^j)
     uint32_t xinv[1024];    // x^(-8 p)
     uint32_t pos[132][256]; // k_entries, tiny phase: row r = X^(r-3)(byte), rows 0..3 (m <= 0) zero
-    // The same rows laid out for conflict-free lookups (tiny phase, RAMCRC_TINY_CF):
-    // word 128 (255 - b) + (128 - m) = X^m(b), m = 1 .. 128, then 128 zero words.
-    uint32_t post[256 * 128 + 128];
     uint32_t xmeta[5 * 64 + 1];   // k_seg_walk: x^(8d), d = 0 .. 320 (one batch of metadata)
     uint32_t xbyte[4][256];       // x^(8 * b * 256^j): x^(8d) for any 32-bit d in 4 factors
-    alignas(16) OpTable xinv128;  // tiny phase: X^-128 (a window sum moved back from the window end)
-    // Bases the tiny phase builds its LDS tables from (tiny_fill_gen):
+    // Bases the tiny phase builds its LDS tables from (tiny_fill_build):
     // twb[q][k] = X^(128 - q)(1 << k), twib[j][k] = X^-128(1 << (8 j + k))
     alignas(16) uint32_t twb[128][8];
     alignas(16) uint32_t twib[4][8];
@@ -84,10 +73,8 @@ constexpr DeviceTables make_device_tables()
     }
     for (int m = 1; m <= 128; m++) {
         const uint32_t c = ramcrc::xpow8(uint64_t(m));
-        for (uint32_t b = 0; b < 256; b++) {
+        for (uint32_t b = 0; b < 256; b++)
             t.pos[m + 3][b] = ramcrc::mulmod(b, c);
-            t.post[128 * (255 - b) + (128 - m)] = t.pos[m + 3][b];
-        }
     }
     for (int d = 0; d <= 5 * 64; d++)
         t.xmeta[d] = ramcrc::xpow8(uint64_t(d));
@@ -100,13 +87,16 @@ constexpr DeviceTables make_device_tables()
         }
     }
     {
+        // X^-128 (a window sum moved back from the window end): only its
+        // basis words go to the device
+        OpTable xinv128{};
         const uint32_t c = ramcrc::xinv8pow(128);
         for (int k = 0; k < 4; k++)
             for (uint32_t b = 0; b < 256; b++)
-                t.xinv128.t[k][b] = ramcrc::mulmod(b << (8 * k), c);
+                xinv128.t[k][b] = ramcrc::mulmod(b << (8 * k), c);
         for (int k = 0; k < 4; k++)
             for (int j = 0; j < 8; j++)
-                t.twib[k][j] = t.xinv128.t[k][1u << j];
+                t.twib[k][j] = xinv128.t[k][1u << j];
     }
     for (int q = 0; q < 128; q++) {
         const uint32_t c = ramcrc::xpow8(uint64_t(128 - q));
@@ -233,13 +223,9 @@ __device__ __forceinline__ void fill_plain(uint8_t* lds, uint32_t off, const uin
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 {
-#if RAMCRC_ASM_XOR3
     uint32_t r;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-#else
-    return a ^ b ^ c;
-#endif
 }
 
 // Per-lane constant for table k: [byte0 = bank offset (+128 for odd k),
@@ -385,13 +371,9 @@ __device__ __forceinline__ uint32_t load_u32_any(uint64_t a)
     return __builtin_amdgcn_alignbyte(w1, w0, uint32_t(a) & 3);
 }
 
-#ifndef RAMCRC_STEP_BATCH
-#define RAMCRC_STEP_BATCH 1
-#endif
 __device__ __forceinline__ void RepOp::apply4(const uint8_t* lds, uint32_t& u0, uint32_t& u1,
                                               uint32_t& u2, uint32_t& u3, const u32x4& w) const
 {
-#if RAMCRC_STEP_BATCH
     auto rd = [&](uint32_t a) { return *reinterpret_cast<const uint32_t*>(lds + a); };
     uint32_t a0 = rd(rep_addr<0>(u0, lr0)), a1 = rd(rep_addr<1>(u0, lr1));
     uint32_t a2 = rd(rep_addr<2>(u0, lr2)), a3 = rd(rep_addr<3>(u0, lr3));
@@ -408,12 +390,6 @@ __device__ __forceinline__ void RepOp::apply4(const uint8_t* lds, uint32_t& u0, 
     u1 = xor3(xor3(b0, b1, w.y), b2, b3);
     u2 = xor3(xor3(c0, c1, w.z), c2, c3);
     u3 = xor3(xor3(d0, d1, w.w), d2, d3);
-#else
-    u0 = apply(lds, u0, w.x);
-    u1 = apply(lds, u1, w.y);
-    u2 = apply(lds, u2, w.z);
-    u3 = apply(lds, u3, w.w);
-#endif
 }
 
 // ------------------------------------------------------------ descriptors
@@ -561,7 +537,6 @@ struct Plan {
     uint32_t* partials;
     uint64_t partials_cap;
     uint32_t* status;      // bit 0: this launch's partials overflow; bit 1: sticky (ramcrc_ctx_check)
-    unsigned long long* ticket;   // chunk dequeue counter; zero between launches
     const uint32_t* nlarge;       // nullable: large buffers counted by this sequence's
                                   // k_bin_count; 0 -> every plan kernel exits at once
 };

@@ -151,7 +151,7 @@ __device__ unsigned long long g_stamps[kStampWaves * kStampSlots];
     } while (0)
 #endif
 
-// The tiny phases with conflict-free table lookups (RAMCRC_TINY_CF): the
+// The tiny phases with conflict-free table lookups: the
 // window-relative table below puts a lookup's LDS bank on its window position,
 // whatever the data byte.  Lane u of a group holds the window dwords u, u + 8,
 // u + 16, u + 24 (window offsets 32 j + 4 u), so the 8 lanes of a group read
@@ -224,37 +224,6 @@ __device__ __forceinline__ uint32_t tw_addr(uint32_t q, uint32_t b)
     return ((q >> 6) << 16) | (b << 8) | ((q & 63) << 2);
 }
 
-__device__ __forceinline__ void tiny_fill_wr(uint8_t* lds)
-{
-    // 8192 chunks of 16 B, chunk (h, b, c) = words 128 (255 - b) + 64 h + 4 c .. of
-    // g_tab.post (X^m(b) at 128 (255 - b) + 128 - m), then the X^-128 table
-    constexpr uint32_t kPos = 8192, kAll = kPos + 256;
-    constexpr uint32_t kPer = (kAll + kEntWaves * kWaveSize - 1) / (kEntWaves * kWaveSize);
-    const uint4* post = reinterpret_cast<const uint4*>(g_tab.post);
-    const uint4* inv = reinterpret_cast<const uint4*>(&g_tab.xinv128);
-    uint4 v[kPer];
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const uint32_t i = threadIdx.x + j * (kEntWaves * kWaveSize);
-        if (i < kPos) {
-            const uint32_t h = i >> 12, b = (i >> 4) & 255, c = i & 15;
-            v[j] = post[(128 * (255 - b) + 64 * h) / 4 + c];
-        } else if (i < kAll) {
-            v[j] = inv[i - kPos];
-        }
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const uint32_t i = threadIdx.x + j * (kEntWaves * kWaveSize);
-        if (i < kAll)
-            *reinterpret_cast<uint4*>(lds + 16 * i) = v[j];
-    }
-}
-
-#ifndef RAMCRC_TINY_GEN
-#define RAMCRC_TINY_GEN 1   // tiny tables built in LDS from 8 basis words per row (0: copied from g_tab)
-#endif
-#if RAMCRC_TINY_GEN
 // The tiny phases' tables built in place instead of copied: X^m is linear, so
 // row q of X^(128 - q)(b) is the XOR of the basis words twb[q][k] over the set
 // bits k of b.  Thread t takes row q = t % 128 and the 32 columns b0 .. b0 + 31,
@@ -315,11 +284,10 @@ __device__ __forceinline__ void tiny_fill_build(uint8_t* lds, const TinyBasis& t
     }
 }
 
-__device__ __forceinline__ void tiny_fill_gen(uint8_t* lds)
+__device__ __forceinline__ void tiny_fill(uint8_t* lds)
 {
     tiny_fill_build(lds, tiny_basis_load());
 }
-#endif
 
 // Per-lane address constants: byte k of a rotated dword (window position
 // 32 j + 4 u + ((k + g4) & 3)) of dword pair j >> 1; + 128 for odd j.
@@ -368,13 +336,9 @@ __device__ __forceinline__ uint32_t tiny_win_wr(const uint8_t* lds, const u32x4&
     for (int j = 0; j < 4; j++) {
         uint32_t keep = 0xFFFFFFFFu;
         if (!kTail3 || j == 3) {
-#if RAMCRC_TINY_MED3
             // one v_med3 after the add (the compiler's max/add/min is three ops)
             uint32_t sh;
             asm("v_med3_i32 %0, %1, 0, 32" : "=v"(sh) : "v"(z + 256 * j));
-#else
-            const uint32_t sh = uint32_t(min(max(z + 256 * j, 0), 32));
-#endif
             keep = uint32_t(uint64_t(0xFFFFFFFFu) >> sh);
         }
         if (j == 0)
@@ -402,15 +366,6 @@ __device__ __forceinline__ uint32_t tiny_win_wr(const uint8_t* lds, const u32x4&
     uint32_t R = xor3(xor3(t0, t1, t2), xor3(t3, t4, v[15]), 0u);
     R = group8_xor_all(R);
     return R;
-}
-
-__device__ __forceinline__ void tiny_fill(uint8_t* lds)
-{
-#if RAMCRC_TINY_GEN
-    tiny_fill_gen(lds);
-#else
-    tiny_fill_wr(lds);
-#endif
 }
 
 // X^m(v) for 4 <= m <= 128 (byte k at distance m - k), and X^-128(v)
@@ -517,7 +472,7 @@ __device__ __forceinline__ bool tiny_run_cf(const BatchDesc& d, const Sorted& so
             const uint64_t A = (geo[q] & 0xFFF) ? (Sq & ~uint64_t(15)) : dummy;
             [[maybe_unused]] const uint64_t au = A + 4 * gl;
             u32x4 v;
-            if (RAMCRC_TINY_SAFE && __builtin_amdgcn_ballot_w64(!((geo[q] >> 12) & 1)) == 0) {
+            if (__builtin_amdgcn_ballot_w64(!((geo[q] >> 12) & 1)) == 0) {
                 // every window of this q is page-safe: plain loads, immediate offsets
                 v.x = *reinterpret_cast<g32*>(au);
                 v.y = *reinterpret_cast<g32*>(au + 32);
@@ -535,46 +490,26 @@ __device__ __forceinline__ bool tiny_run_cf(const BatchDesc& d, const Sorted& so
         });
     };
 
-    // RAMCRC_TINY_OVL: the table's basis words are loaded first, round 0's
-    // windows issued as soon as its owners are known, and the table built
-    // while those loads are in flight (the build waits for the basis alone)
-    constexpr bool kOvl = RAMCRC_TINY_OVL && RAMCRC_TINY_GEN;
-#if RAMCRC_TINY_GEN
-    TinyBasis tb;
-    if constexpr (kOvl)
-        tb = tiny_basis_load();
-#endif
+    // The table's basis words are loaded first, round 0's windows issued as
+    // soon as its owners are known, and the table built while those loads are
+    // in flight (the build waits for the basis alone)
+    const TinyBasis tb = tiny_basis_load();
     uint64_t r = wave;
     TinyOwn o0 = load_own(r), o1 = load_own(r + nwaves);
     u32x4 wc[8];
     uint32_t gc[8], sc;
-#if RAMCRC_TINY_GEN
-    if constexpr (kOvl) {
-        issue(o0, wc, gc, sc);
-        tiny_fill_build(lds, tb);
-    } else {
-        tiny_fill(lds);
-    }
-#else
-    tiny_fill(lds);
-#endif
+    issue(o0, wc, gc, sc);
+    tiny_fill_build(lds, tb);
     const TwRows rw(gl, g4);
-    // without the register prefetch the selectors fit (RAMCRC_TINY_LSEL 2)
-    // with the prefetch, the windows' geometry is swizzled again from the
-    // owner in the compute (RAMCRC_TINY_REGEO) so that the selectors and the
-    // second window body fit in the registers
-    constexpr bool kRegeo = kPF && RAMCRC_TINY_REGEO;
-    constexpr bool kLean = !kPF || kRegeo;
-    constexpr bool kLsel = RAMCRC_TINY_LSEL == 2 ? kLean : bool(RAMCRC_TINY_LSEL);
-    TwSel ts;
-    if constexpr (kLsel)
-        ts = TwSel(g4);
+    // per-lane v_perm selectors instead of a v_alignbyte per dword: without
+    // the register prefetch they fit; with the prefetch, the windows' geometry
+    // is swizzled again from the owner in the compute so that the selectors
+    // and the second window body fit in the registers
+    const TwSel ts(g4);
     if (__syncthreads_or(bad))
         return false;
     RAMCRC_STAMP(5);
     bool first_round = true;
-    if constexpr (!kOvl)
-        issue(o0, wc, gc, sc);
     for (; r < rounds; r += nwaves) {
         const TinyOwn o2 = load_own(r + 2 * nwaves);
         u32x4 wn[8];
@@ -586,13 +521,13 @@ __device__ __forceinline__ bool tiny_run_cf(const BatchDesc& d, const Sorted& so
         uint32_t mine = 0;
         static_for8([&](auto qc) {
             constexpr int q = decltype(qc)::value;
-            const uint32_t g = kRegeo ? swz_from<q>(o0.geo) : gc[q];
+            const uint32_t g = kPF ? swz_from<q>(o0.geo) : gc[q];
             const uint32_t sa = (g >> 8) & 0xF;
             const uint32_t e = sa + (g & 0xFF);           // window-relative end, <= 128
             // (a wave-uniform branch: entries of 81 B or more skip most tail masks)
-            const bool t3 = RAMCRC_TINY_T3 && kLean && __builtin_amdgcn_ballot_w64(e < 96) == 0;
-            const uint32_t R = t3 ? tiny_win_wr<kLsel, true>(lds, wc[q], sa, e, rw, gl, g4, ts)
-                                  : tiny_win_wr<kLsel, false>(lds, wc[q], sa, e, rw, gl, g4, ts);
+            const bool t3 = __builtin_amdgcn_ballot_w64(e < 96) == 0;
+            const uint32_t R = t3 ? tiny_win_wr<true, true>(lds, wc[q], sa, e, rw, gl, g4, ts)
+                                  : tiny_win_wr<true, false>(lds, wc[q], sa, e, rw, gl, g4, ts);
             mine = gl == uint32_t(q) ? R : mine;
         });
         // own slot: the initial state (byte k at distance len - k), or bytewise
@@ -844,8 +779,8 @@ __device__ __forceinline__ void tiny_multi(const BatchDesc& d, const Sorted& so,
                                            uint32_t blk, uint32_t nblk)
 {
     if constexpr (kTinyK >= 2) {
-        if (RAMCRC_TINY_DM && so.bt->direct_multi) {
-            if (RAMCRC_TINY_M2 && kTinyK > 2 && so.bt->direct_multi_k2)
+        if (so.bt->direct_multi) {
+            if (kTinyK > 2 && so.bt->direct_multi_k2)
                 tiny_multi_run<2, 4, true>(d, so, lds, blk, nblk, 0, so.bt->direct_multi);
             else
                 tiny_multi_run<kTinyK, 2, true>(d, so, lds, blk, nblk, 0, so.bt->direct_multi);
@@ -854,7 +789,7 @@ __device__ __forceinline__ void tiny_multi(const BatchDesc& d, const Sorted& so,
         const uint64_t s0 = so.bt->start[2], s1 = so.bt->start[kTinyK + 1];
         if (s0 == s1)
             return;   // uniform
-        if constexpr (RAMCRC_TINY_M2 && kTinyK > 2) {
+        if constexpr (kTinyK > 2) {
             const uint64_t s2 = so.bt->start[3];
             tiny_multi_run<2, 4>(d, so, lds, blk, nblk, s0, s2);
             tiny_multi_run<kTinyK, 2>(d, so, lds, blk, nblk, s2, s1);
@@ -1073,11 +1008,7 @@ __device__ __forceinline__ void entries_run(const BatchDesc& d, const Sorted& so
             // loads: head, first two tail steps, first kPU interior steps
             const gu32x4* pb = gptr16(steps ? p0 : dummy);
             const uint64_t bstride = steps ? kStep / 16 : 0;
-#if RAMCRC_ENT_NT
             auto ldf = [&](uint64_t k) -> u32x4 { return __builtin_nontemporal_load(pb + k * bstride); };
-#else
-            auto ldf = [&](uint64_t k) -> u32x4 { return pb[k * bstride]; };
-#endif
             auto ldt = [&](uint32_t k) -> u32x4 {   // tail step: lanes past E read a safe word
                 const uint64_t a = p0 + uint64_t(k) * kStep;
                 return load16(k < steps && a < E ? a : safe);
@@ -1320,7 +1251,6 @@ __device__ __forceinline__ void long_phase(const BatchDesc& d, const Sorted& so,
 // loops, so the long-entry loop's registers are not shared with the short one.
 __global__ __launch_bounds__(kEntWaves * kWaveSize, 1) void k_entries(BatchDesc d, Sorted so)
 {
-    static_assert(RAMCRC_TINY_CF, "k_entries runs the conflict-free tiny phases");
     __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsEntries];
     // Every bin must hold exactly the entries the scatter placed in it
     // (cursor == count): then every sorted slot this launch reads was written
@@ -1337,7 +1267,7 @@ __global__ __launch_bounds__(kEntWaves * kWaveSize, 1) void k_entries(BatchDesc 
     RAMCRC_STAMP(0);
     const bool have_tk = kTinyK >= 2 && !so.bt->direct_n &&
                          (so.bt->direct_multi || so.bt->start[kTinyK + 1] != so.bt->start[2]);
-    // Role split (round 5, RAMCRC_SPLIT): when a batch has both tiny and long
+    // Role split: when a batch has both tiny and long
     // entries, workgroups < T run only the tiny phases (filling only their
     // table) and the others only the long phase, so the two overlap and no
     // workgroup waits for its slowest tiny wave before refilling its LDS.  T
@@ -1345,7 +1275,7 @@ __global__ __launch_bounds__(kEntWaves * kWaveSize, 1) void k_entries(BatchDesc 
     // units.  T = 0: both phases on every workgroup, in sequence.
     uint32_t T = 0;
     constexpr int kT = kTinyK > kSmallK ? kTinyK : kSmallK;
-    if (RAMCRC_SPLIT && !so.bt->direct_n && so.bt->start[kTinyK + 1] != so.bt->start[0] &&
+    if (!so.bt->direct_n && so.bt->start[kTinyK + 1] != so.bt->start[0] &&
         so.bt->items[kNB] != so.bt->items[kT + 1]) {
         uint64_t win = so.bt->start[2] - so.bt->start[0];   // one window each
         for (int b = 2; b <= kTinyK; b++)
@@ -1360,7 +1290,7 @@ __global__ __launch_bounds__(kEntWaves * kWaveSize, 1) void k_entries(BatchDesc 
     if (do_tiny) {
         // records (replay) keep the register prefetch: without it their
         // tiny phase measured 3-4 % slower; table batches 5-7 % faster
-        tiny_ok = (RAMCRC_TINY_PF == 2 ? d.rec != nullptr : bool(RAMCRC_TINY_PF))
+        tiny_ok = d.rec != nullptr
                       ? tiny_run_cf<true>(d, so, lds, bad, blockIdx.x, tn, have_tk)
                       : tiny_run_cf<false>(d, so, lds, bad, blockIdx.x, tn, have_tk);
         if (tiny_ok && have_tk)

@@ -54,7 +54,9 @@ struct ramcrc_ctx {
     uint32_t dirty_bins = 0;    // RAMCRC_OPT_TEST_DIRTY_BINS: bin << 16 | count, once
     int bin_straggler = 0;      // RAMCRC_OPT_TEST_BIN_STRAGGLER: next k_bin_one waits in vain
     int bin_resident[5] = {-1, -1, -1, -1, -1};   // k_bin_one<mode> workgroups per CU (occupancy query)
-    int bin_one = RAMCRC_BIN_ONE;   // RAMCRC_OPT_BIN_ONE: k_bin_one for batches of one tile per workgroup
+    // RAMCRC_OPT_BIN_ONE: k_bin_one for batches of <= 1 tile per workgroup; off
+    // since round 6, the two-launch binning measured equal or faster
+    int bin_one = 0;
     u32x4* sdesc = nullptr;
     uint32_t* sidx = nullptr;
     uint32_t* sinit = nullptr;
@@ -162,7 +164,6 @@ Plan make_plan(ramcrc_ctx* c, uint64_t n)
     pl.partials = c->partials;
     pl.partials_cap = c->partials_cap;
     pl.status = c->status;
-    pl.ticket = reinterpret_cast<unsigned long long*>(c->status + 2);   // 8-byte aligned
     return pl;
 }
 
@@ -173,13 +174,9 @@ Plan make_plan(ramcrc_ctx* c, uint64_t n)
 // elapsed time is read only after the stream is synchronised.
 constexpr unsigned kTimerEventFlags = hipEventDisableSystemFence;
 
-#ifndef RAMCRC_EXT_TIMING
-#define RAMCRC_EXT_TIMING 1
-#endif
-// Times the one launch of its scope.  With RAMCRC_EXT_TIMING the two events
-// ride in the kernel's own dispatch (hipExtLaunchKernelGGL start/stop
-// events): no separate event packets, so no stream bubble before and after
-// the kernel; otherwise they are recorded around it.
+// Times the one launch of its scope.  The two events ride in the kernel's own
+// dispatch (hipExtLaunchKernelGGL start/stop events): no separate event
+// packets, so no stream bubble before and after the kernel.
 struct ScanTimer {
     ramcrc_ctx* c;
     hipStream_t s;
@@ -194,26 +191,20 @@ struct ScanTimer {
         } else if (hipEventCreateWithFlags(&ev.first, kTimerEventFlags) != hipSuccess ||
                    hipEventCreateWithFlags(&ev.second, kTimerEventFlags) != hipSuccess) {
             ev = {nullptr, nullptr};
-            return;
         }
-        if (!RAMCRC_EXT_TIMING)
-            (void)hipEventRecord(ev.first, s);
     }
     template <typename F, typename... Args>
     void launch(F kernel, dim3 grid, dim3 block, Args... args)
     {
-        if (RAMCRC_EXT_TIMING && ev.first)
+        if (ev.first)
             hipExtLaunchKernelGGL(kernel, grid, block, 0, s, ev.first, ev.second, 0, args...);
         else
             hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
     }
     ~ScanTimer()
     {
-        if (!ev.first)
-            return;
-        if (!RAMCRC_EXT_TIMING)
-            (void)hipEventRecord(ev.second, s);
-        c->ev_used.push_back(ev);
+        if (ev.first)
+            c->ev_used.push_back(ev);
     }
 };
 

@@ -58,7 +58,6 @@ __global__ __launch_bounds__(kThreads) void k_plan_scan(Plan pl)
         // stream-ordered before this launch's k_chunks; atomic so that a
         // sticky bit set concurrently by another stream's launch survives
         atomicAnd(pl.status, ~kStatusRefused);
-        *pl.ticket = 0;
     }
     if (plan_empty(pl)) {
         if (threadIdx.x == 0)

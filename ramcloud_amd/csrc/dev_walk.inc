@@ -468,13 +468,7 @@ __device__ __forceinline__ PWalk walk_geo(PWalk w)
 // round(log2(64 m)) within [kPartShift, kPartShiftMax].  A forced shift
 // (RAMCRC_OPT_WALK_PART_SHIFT) is written as is.
 constexpr uint32_t kPartShiftMax = 20;
-#ifndef RAMCRC_SKIP_P17
-#define RAMCRC_SKIP_P17 1   // the probe never picks 128 KiB parts (0: it may)
-#endif
 constexpr int kProbeHops = 8;
-#ifndef RAMCRC_SYNC_ADAPT
-#define RAMCRC_SYNC_ADAPT 1   // k_walk_sync's stage sized from the probe's mean entry (0: always 7 KiB)
-#endif
 constexpr uint32_t kPartShiftLow = kPartShift;   // the smallest part the probe picks
 
 // The replay summary word (PWalk::sum, replay_hard bits) only gains bits
@@ -498,9 +492,6 @@ __device__ __forceinline__ uint32_t walk_sum_seen(const uint32_t* sum)
 // go to a list k_left checks one lane per record; any record neither can take
 // (an object of 64 KiB or more, a segment the serial walker took, a full
 // list) sets kHardFull, and then the usual verify runs over the whole table.
-#ifndef RAMCRC_VFAST
-#define RAMCRC_VFAST 1   // verify in the walk for small entries (0: never)
-#endif
 #ifndef RAMCRC_FAST_MEAN
 #define RAMCRC_FAST_MEAN 176   // largest mean entry (bytes, probe) that takes it: 64 of
                                // them (a block of records) fit k_walk_copyv's 12 KiB stage
@@ -574,22 +565,22 @@ __global__ __launch_bounds__(kWaveSize) void k_walk_probe(PWalk w, uint32_t forc
             // the sync search's six validation hops leave its 7 KiB stage
             // and chase through global memory -- and 4 KiB -12 %): the
             // entries that round to them (≈ 1.45 .. 2.9 KiB) take 256 KiB
-            if (shift == 17 && RAMCRC_SKIP_P17)
+            if (shift == 17)
                 shift = 18;
         }
         *geo = shift;
-        // the sync search's stage (k_walk_sync): RAMCRC_SYNC_ADAPT sizes it for
-        // 16 mean entries (1 KiB .. kSyncStage) -- a dense batch's six-hop
+        // the sync search's stage (k_walk_sync) is sized for 16 mean entries
+        // (1 KiB .. kSyncStage; a forced shift keeps kSyncStage) -- a dense batch's six-hop
         // chains fit a few hundred bytes, and every staged byte is read again
         // by the part walk
         uint32_t sstage = kSyncStage;
-        if (RAMCRC_SYNC_ADAPT && !forced && hops) {
+        if (!forced && hops) {
             const uint64_t want = ((16 * (dist / hops)) + 1023) & ~uint64_t(1023);
             sstage = uint32_t(want < 1024 ? 1024 : (want > kSyncStage ? kSyncStage : want));
         }
         geo[1] = sstage;
         if (w.sum) {
-            const bool fast = RAMCRC_VFAST && w.obj_crc && w.nleft &&
+            const bool fast = w.obj_crc && w.nleft &&
                               (w.vmode == 2 || (hops && dist <= uint64_t(kFastMean) * hops));
             const bool small = hops && dist <= uint64_t(kFastMean8) * hops;
             *w.sum = fast ? (kSumFast | (small ? kSumStage8 : 0u)) : 0u;
@@ -602,9 +593,6 @@ __global__ __launch_bounds__(kWaveSize) void k_walk_probe(PWalk w, uint32_t forc
 // a few KiB) read LDS instead of waiting on global memory.
 constexpr uint32_t kSyncWin = kSyncStage - 16;       // candidates / hops read from LDS below this
 constexpr int kSyncWaves = 4;                        // waves per workgroup
-#ifndef RAMCRC_SYNC_TYPES
-#define RAMCRC_SYNC_TYPES 1   // k_walk_sync: survivors whose hops are all objects / tombstones first
-#endif
 constexpr uint64_t kSyncJunkKey = 1ull << 63;        // search key bit: a survivor of the other class
 
 // Wave minimum through DPP (quad swaps, half-row and row mirrors, row
@@ -640,16 +628,6 @@ __device__ __forceinline__ SyncPart sync_part(const PWalk& w, uint64_t i)
     return P;
 }
 
-#ifndef RAMCRC_SYNC_PF
-#define RAMCRC_SYNC_PF 1   // stage loads of a wave's next part issued before this part's search
-#endif
-#ifndef RAMCRC_SYNC_STRICT
-#define RAMCRC_SYNC_STRICT 1   // candidate hops past the walk limit or of empty entries end the candidate
-#endif
-#ifndef RAMCRC_SYNC_EARLY
-#define RAMCRC_SYNC_EARLY 1   // stop at the end of the first round holding a survivor
-#endif
-
 __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
 {
     const PWalk w = walk_geo(w0);
@@ -664,7 +642,7 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
     const uint64_t total = w.nseg * w.nparts;
     // stage [B, B + kSyncStage): bytes at or past the capacity are 0.  All
     // loads are issued before the first store (one memory latency, not one
-    // per 1 KiB); with RAMCRC_SYNC_PF the loads of the wave's next part are
+    // per 1 KiB), and the loads of the wave's next part are
     // in flight while this part is searched.  The LDS is wave-private.
     u32x4 v[kSU];
     // staged bytes of this batch (a multiple of 1 KiB, at most kSyncStage)
@@ -679,13 +657,13 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
     };
     uint64_t i = uint64_t(blockIdx.x) * kSyncWaves + wv;
     SyncPart nxt{};
-    if (RAMCRC_SYNC_PF && i < total) {
+    if (i < total) {
         nxt = sync_part(w, i);
         if (nxt.k != 0)
             stage_load(nxt);
     }
     for (; i < total; i += nwave) {
-        const SyncPart P = RAMCRC_SYNC_PF ? nxt : sync_part(w, i);
+        const SyncPart P = nxt;
         const uint32_t B = P.B;
         const uint64_t sb = P.sb;
         const uint32_t limit = P.seglen < w.capacity ? P.seglen : w.capacity;   // walk_limit
@@ -695,14 +673,12 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
         const uint32_t end = uint32_t(end64 < limit ? end64 : limit);
         const bool search_part = P.k != 0 && end > B;   // part 0 starts at offset 0
         if (search_part) {
-            if (!RAMCRC_SYNC_PF)
-                stage_load(P);
 #pragma unroll
             for (uint32_t u = 0; u < kSU; u++)
                 if (u * 1024 < ss)
                     *reinterpret_cast<u32x4*>(win + u * 1024 + uint32_t(lane) * 16) = v[u];
         }
-        if (RAMCRC_SYNC_PF && i + nwave < total) {
+        if (i + nwave < total) {
             nxt = sync_part(w, i + nwave);
             if (nxt.k != 0)   // (also for a part past the segment length: not known yet)
                 stage_load(nxt);
@@ -731,13 +707,13 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
         // (ties: the lower candidate; a junk chain that wins has met the real
         // chain within two entries, which k_walk_fix resolves in as many
         // hops).  The scan ends with the first round that holds a survivor
-        // (RAMCRC_SYNC_EARLY; a junk survivor from an earlier position is then
+        // (a junk survivor from an earlier position is then
         // met by k_walk_fix or its part walked again), or else at the nearest
         // first hop seen.  The guess only decides how much k_walk_fix re-walks,
         // never a result.  Replay A/B (profiles/r03/walk): stopping early cut
         // this kernel from 217 to 157 us on 1 KiB objects, but with the
         // permissive hop test alone it doubled k_walk_fix (more junk guesses);
-        // with the strict test (RAMCRC_SYNC_STRICT) the step is 4.8 % faster.
+        // with the strict test (see the hop loop) the step is 4.8 % faster.
         // Per round: lane l filters candidates c0 + 8 l + j (j < 8) four at a
         // time with byte-parallel (SWAR) tests on the words it holds
         // (first_hop4); the ~10 % that pass are listed in LDS and chased one
@@ -761,7 +737,7 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
             uint64_t best = ~0ull;                // (position after two hops << 32) | candidate
             uint32_t bound = 0xFFFFFFFFu;         // nearest first hop of a survivor: h lies below it
             // (early stop: once a survivor of the preferred class is known)
-            for (uint32_t c0 = B; c0 < to && c0 < bound && !(RAMCRC_SYNC_EARLY && best < kSyncJunkKey);
+            for (uint32_t c0 = B; c0 < to && c0 < bound && !(best < kSyncJunkKey);
                  c0 += kSyncRound) {
                 const uint32_t cl = c0 + uint32_t(lane) * kSyncPer;
                 constexpr int kWords = (kSyncPer / 4 + 3) & ~1;
@@ -810,8 +786,7 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
                                 // neither crosses the segment length nor holds an
                                 // empty entry -- junk chains through structured
                                 // object headers do both)
-                                if (plausible(q, h, w.capacity) &&
-                                    (!RAMCRC_SYNC_STRICT || (h.next <= limit && h.len != 0))) {
+                                if (plausible(q, h, w.capacity) && h.next <= limit && h.len != 0) {
                                     p = uint32_t(h.next);
                                     const uint32_t ty = uint32_t(q) & 0x3F;
                                     junk = junk || (ty != RAMCRC_LOG_ENTRY_TYPE_OBJ &&
@@ -833,12 +808,12 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
                     const uint32_t fb = wave_min(live ? first : 0xFFFFFFFFu);
                     bound = fb < bound ? fb : bound;
                     // nearest second hop, ties to the lower candidate; chains of
-                    // objects and tombstones first (RAMCRC_SYNC_TYPES): a fixed
+                    // objects and tombstones first: a fixed
                     // object layout can hold a junk chain of another type that
                     // runs beside the real one at the same stride and never meets
                     // it, and then beats it on the second hop -- k_walk_fix then
                     // re-walks the whole part (128 B values: 0.37 ms per batch)
-                    for (int cls = RAMCRC_SYNC_TYPES ? 0 : 1; cls < 2; cls++) {
+                    for (int cls = 0; cls < 2; cls++) {
                         const bool lc = live && (cls == 1 || !junk);
                         const uint32_t s2 = wave_min(lc ? second : 0xFFFFFFFFu);
                         if (s2 != 0xFFFFFFFFu) {
@@ -846,7 +821,7 @@ __global__ __launch_bounds__(kSyncWaves * kWaveSize) void k_walk_sync(PWalk w0)
                             const uint32_t lo = __popcll(tie) == 1
                                                     ? uint32_t(__builtin_amdgcn_readlane(int(c), __builtin_ctzll(tie)))
                                                     : wave_min(lc && second == s2 ? c : 0xFFFFFFFFu);
-                            const uint64_t key = (RAMCRC_SYNC_TYPES && cls ? kSyncJunkKey : 0ull) |
+                            const uint64_t key = (cls ? kSyncJunkKey : 0ull) |
                                                  (uint64_t(s2) << 32) | lo;
                             best = key < best ? key : best;
                             break;
@@ -1618,9 +1593,6 @@ __global__ __launch_bounds__(256) void k_walk_emit(PWalk w0)
 // each level's loads for all of them together.
 static_assert(kPartRec == kWaveSize, "k_walk_copy: one lane per record of a block");
 
-#ifndef RAMCRC_COPY_NT
-#define RAMCRC_COPY_NT 1   // k_walk_copy: nontemporal record stores (replay 64 B +1.7 %)
-#endif
 #ifndef RAMCRC_COPY_U
 #define RAMCRC_COPY_U 4
 #endif
@@ -1694,14 +1666,11 @@ __global__ __launch_bounds__(256) void k_walk_copy(PWalk w0)
             const uint64_t dst = sbase[u] + r[u].rec + r[u].pre + (ri - r[u].cut);
             if (dst < w.cap) {
                 const u32x4 rec = {uint32_t(part[u] / w.nparts), v[u].x, v[u].y >> 8, v[u].y & 0xFF};
-#if RAMCRC_COPY_NT
-                // streamed: not read back by this kernel.  (The same for the
-                // part walk's scratch stores was 8 % slower: k_walk_copy reads
-                // that scratch back while it is still in the caches.)
+                // streamed: not read back by this kernel (replay 64 B +1.7 %
+                // over plain stores).  (The same for the part walk's scratch
+                // stores was 8 % slower: k_walk_copy reads that scratch back
+                // while it is still in the caches.)
                 __builtin_nontemporal_store(rec, &w.entries[dst]);
-#else
-                w.entries[dst] = rec;
-#endif
                 hard |= (seen & kHardAll) != kHardAll ? replay_hard(v[u].x, v[u].y >> 8, v[u].y & 0xFF) : 0u;
             }
         }

@@ -150,7 +150,7 @@ const char* ramcrc_build_info(void)
            " block=1KiB waves/WG=16 unroll=" RAMCRC_STR(RAMCRC_UNROLL)
            " lds_chunks=" RAMCRC_STR(RAMCRC_LDS_CHUNKS) " lds_entries=" RAMCRC_STR(RAMCRC_LDS_ENTRIES)
            " entries: waves=" RAMCRC_STR(RAMCRC_ENT_WAVES) " smallk=" RAMCRC_STR(RAMCRC_SMALLK)
-           " pu=" RAMCRC_STR(RAMCRC_PU) " tiny_cf=" RAMCRC_STR(RAMCRC_TINY_CF)
+           " pu=" RAMCRC_STR(RAMCRC_PU)
            " large_min=64KiB part_shift=" RAMCRC_STR(RAMCRC_PART_SHIFT)
            " defines=" RAMCRC_DEFINES;
 }
@@ -179,6 +179,7 @@ int ramcrc_ctx_create(int device, ramcrc_ctx** out)
     c->device = device;
     c->ncu = prop.multiProcessorCount;
     c->ncu_all = c->ncu;
+    // four words: [0] the status bits, [1] k_status_take's copy for the host, [2..3] spare
     if (hipMalloc(reinterpret_cast<void**>(&c->status), 16) != hipSuccess) {
         delete c;
         return RAMCRC_ENOMEM;

@@ -183,7 +183,7 @@ def test_all_tiny_batch_direct_path(ctx, ramcrc, oracle_mod, api):
 @pytest.mark.parametrize("api", ["entries", "batch"])
 def test_direct_path_long_windows(ctx, ramcrc, oracle_mod, api):
     """All-tiny batches whose windows mostly end at >= 96 bytes, where the
-    tiny loop skips the tail masks of dwords 0-2 (RAMCRC_TINY_T3, a ballot
+    tiny loop skips the tail masks of dwords 0-2 (a ballot
     per q): entries of 81-112 bytes at every alignment, then 60-112 bytes so
     that waves mix the masked and unmasked window bodies, with and without
     initial states."""

@@ -3,7 +3,7 @@ RAMCRC_TINY_WR and RAMCRC_TINY_LD16): the one-v_perm address of every lookup
 equals the table position it must read, the 32 lanes of a half-wave read 32
 distinct banks at every lookup instruction, and the fill writes every position
 exactly once inside the 128 KiB table.  The formulas are restated from the
-kernel source (TwRows, tiny_win_wr, tw_addr, tiny_fill_wr)."""
+kernel source (TwRows, tiny_win_wr, tw_addr, tiny_fill_build)."""
 
 
 def perm(s0, s1, sel):
