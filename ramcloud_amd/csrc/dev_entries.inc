@@ -1272,10 +1272,13 @@ __global__ __launch_bounds__(kEntWaves * kWaveSize, 1) void k_entries(BatchDesc 
     // table) and the others only the long phase, so the two overlap and no
     // workgroup waits for its slowest tiny wave before refilling its LDS.  T
     // follows the work: a tiny window costs kSplitKappa / 1024 long-phase work
-    // units.  T = 0: both phases on every workgroup, in sequence.
+    // units.  T = 0: both phases on every workgroup, in sequence -- also the
+    // only choice for a grid of one workgroup (a context sized for one CU),
+    // where a split of T = 1 left nobody for the long phase: its entries'
+    // outputs were never written, with no error.
     uint32_t T = 0;
     constexpr int kT = kTinyK > kSmallK ? kTinyK : kSmallK;
-    if (!so.bt->direct_n && so.bt->start[kTinyK + 1] != so.bt->start[0] &&
+    if (gridDim.x > 1 && !so.bt->direct_n && so.bt->start[kTinyK + 1] != so.bt->start[0] &&
         so.bt->items[kNB] != so.bt->items[kT + 1]) {
         uint64_t win = so.bt->start[2] - so.bt->start[0];   // one window each
         for (int b = 2; b <= kTinyK; b++)

@@ -15,6 +15,7 @@
 //                     tables generated from the polynomial at compile time.
 #include "ramcrc.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 #include "gf2.h"
@@ -242,10 +243,27 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
     const uint64_t src_bytes = n_seg * seg_stride, out_bytes = n_out * out_stride;
     if (sb < ob + out_bytes && ob < sb + src_bytes)
         return RAMCRC_EINVAL;   // the outputs would overwrite the source
-    for (uint64_t i = 0; i < n_place; i++) {
-        if (place[i].record >= n_entries || place[i].partition >= n_part ||
-            (i && place[i].record < place[i - 1].record) ||
-            entries[place[i].record].segment >= n_seg)
+    if (n_place) {
+        // a segment's placements are one run of the list, as k_app_mark demands
+        // (a table whose segments are not contiguous runs is not a walk's)
+        uint8_t* const seen = static_cast<uint8_t*>(calloc((n_seg + 7) / 8, 1));
+        if (!seen)
+            return RAMCRC_ENOMEM;
+        bool ok = true;
+        for (uint64_t i = 0; i < n_place && ok; i++) {
+            ok = place[i].record < n_entries && place[i].partition < n_part &&
+                 (!i || place[i].record >= place[i - 1].record) &&
+                 entries[place[i].record].segment < n_seg;
+            if (!ok)
+                break;
+            const uint32_t seg = entries[place[i].record].segment;
+            if (!i || entries[place[i - 1].record].segment != seg) {
+                ok = !(seen[seg >> 3] & (1u << (seg & 7)));
+                seen[seg >> 3] |= uint8_t(1u << (seg & 7));
+            }
+        }
+        free(seen);
+        if (!ok)
             return RAMCRC_EINVAL;
     }
     uint8_t* const o = static_cast<uint8_t*>(out);

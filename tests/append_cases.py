@@ -69,14 +69,30 @@ def expected(src, stride, table, status, place, n_seg, n_part, cap):
         if flags[k] != segments.SEG_OK:
             continue
         lb = len_bytes(ln)
-        if (hdr & 0x100) or len(outs[k]) + 1 + lb + ln > cap:
+        start = off + 1 + ((hdr >> 6) & 3) + 1
+        # a record flagged OVERLONG, or whose payload runs past its segment's
+        # stride, never fits (include/ramcrc.h)
+        if (hdr & 0x100) or start + ln > stride or len(outs[k]) + 1 + lb + ln > cap:
             flags[k] = segments.SEG_APPEND_FULL
             continue
-        p = seg * stride + off + 1 + ((hdr >> 6) & 3) + 1
+        p = seg * stride + start
         outs[k] += bytes([(hdr & 0x3F) | ((lb - 1) << 6)]) + ln.to_bytes(lb, "little")
         outs[k] += src[p:p + ln].tobytes()
         counts[k] += 1
     return outs, flags, counts
+
+
+def damage_record(table, rec, damage, stride):
+    """Edits record `rec` of a walk table (a numpy array, or a device tensor
+    holding the same words) so that it can never be appended: the OVERLONG
+    flag in its header word, or a length that runs its payload one byte past
+    the segment stride."""
+    if damage == "overlong_flag":
+        table[rec, 3] |= 0x100
+    else:
+        assert damage == "payload_past_stride"
+        off, hdr = int(table[rec, 1]), int(table[rec, 3])
+        table[rec, 2] = stride - (off + 1 + ((hdr >> 6) & 3) + 1) + 1
 
 
 def expected_cert(oracle, data):
@@ -207,3 +223,72 @@ def capacity_case(oracle, seed=19):
 
 def small_mixed(oracle, nseg, seed):
     return segment_cases.mixed_segments(oracle, nseg, 64 * KiB, seed=seed)[:2]
+
+
+# ------------------------------------------------ device calls (GPU tests)
+# Shared by test_gpu_recovery_append.py and test_gpu_small_grid.py; torch is
+# imported where it is used, so the host tests import this module without it.
+PATTERN = 0x5A5A5A5A
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+class Walked:
+    """Source segments on the device with the walk's status and record table."""
+
+    def __init__(self, ctx, buf, certs, cap, nseg, min_entry=2, d_buf=None):
+        import torch
+        self.buf, self.cap, self.nseg = buf, cap, nseg
+        self.d = torch.from_numpy(buf).cuda() if d_buf is None else d_buf
+        dc = torch.from_numpy(np.ascontiguousarray(certs, np.uint32).view(np.int32)).cuda()
+        ecap = nseg * (cap // min_entry + 1)
+        self.d_status = torch.zeros((nseg, 4), dtype=torch.int32, device="cuda")
+        self.d_entries = torch.zeros((ecap, 4), dtype=torch.int32, device="cuda")
+        self.d_n = torch.zeros(1, dtype=torch.int64, device="cuda")
+        ctx.segment_walk(self.d, cap, cap, nseg, dc, self.d_status, self.d_entries, self.d_n)
+        ctx.check()
+        n = int(self.d_n.item())
+        assert n <= ecap
+        self.status = _u32(self.d_status)
+        self.table = np.ascontiguousarray(_u32(self.d_entries[:n]))
+
+
+def _launch(ctx, w, place, n_part, out_capacity, out_stride, place_cap=None, n_place=None):
+    import torch
+    place = np.ascontiguousarray(place, np.uint32).reshape(-1, 2)
+    pcap = place.shape[0] if place_cap is None else place_cap
+    d_place = torch.zeros((max(pcap, 1), 2), dtype=torch.int32, device="cuda")[:pcap]
+    if place.shape[0]:
+        d_place[:place.shape[0]] = torch.from_numpy(place.view(np.int32)).cuda()[:pcap]
+    d_np = torch.tensor([place.shape[0] if n_place is None else n_place], dtype=torch.int64,
+                        device="cuda")
+    n_out = w.nseg * n_part
+    out = torch.full((n_out * out_stride,), FILL, dtype=torch.uint8, device="cuda")
+    certs = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
+    stat = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
+    ctx.recovery_append(w.d, w.cap, w.nseg, w.d_status, w.d_entries, w.d_n, d_place, d_np, n_part,
+                        out, out_stride, out_capacity, certs, stat)
+    return out, certs, stat
+
+
+def _append(ctx, ramcrc, oracle, w, place, n_part, out_capacity, out_stride=None, exp=None,
+            what=""):
+    """One device call checked against the expectation and the host form."""
+    if callable(place):
+        place = place(w.table)
+    place = np.ascontiguousarray(place, np.uint32).reshape(-1, 2)
+    out_stride = out_stride or (out_capacity + 15) // 16 * 16
+    d_out, d_certs, d_stat = _launch(ctx, w, place, n_part, out_capacity, out_stride)
+    ctx.check()
+    out, certs, stat = d_out.cpu().numpy(), _u32(d_certs), _u32(d_stat)
+    if exp is None:
+        exp = expected(w.buf, w.cap, w.table, w.status, place, w.nseg, n_part, out_capacity)
+    check_outputs(oracle, exp, out, out_stride, out_capacity, certs, stat, what)
+    h_out = np.full(out.size, FILL, np.uint8)
+    h_certs, h_stat = ramcrc.recovery_append_host(w.buf, w.cap, w.nseg, w.status, w.table, place,
+                                                  n_part, h_out, out_stride, out_capacity)
+    assert np.array_equal(h_out, out), (what, "host and device outputs differ")
+    assert np.array_equal(h_certs, certs) and np.array_equal(h_stat, stat), what
+    return place, d_out, certs, stat

@@ -193,6 +193,79 @@ def test_entries_every_alignment(ctx, oracle_mod, api):
         assert bad.size == 0, [(offs[i] % 128, ls[i]) for i in bad[:8]]
 
 
+LONG_TOTAL = 96 * MiB
+# (offset, length): 16 MiB + 1 is 65 chunks of 256 KiB, so lane 0 of
+# combine_one takes a second chunk (chunk 64).  combine_one moves chunk k's
+# partial by t = (padded end - end of chunk k) / 1 KiB blocks, and xpow_blocks
+# reads its third factor from t = 65,536 on: chunk 0 of (1, 64 MiB + 1,029)
+# ends at 256 KiB, t = 65,282, still two factors; chunk 0 of (0, 64 MiB +
+# 256 KiB) has t = 65,536 exactly (the third factor alone), the one-byte
+# chunk 0 of (262,143, 64 MiB + 300 KiB) t = 65,836 (first and third), chunk 1
+# of that buffer 65,580.  Small buffers of every path lie between the long ones.
+LONG_BUFFERS = [(5, 16 * MiB + 1), (70, 0), (3, 1), (262144 * 3 + 17, 20 * MiB + 12345),
+                (1000, 100), (77777, 4096), (1, 64 * MiB + 1024 + 5), (123457, 65535),
+                (0, 64 * MiB), (31 * MiB + 9, 70000), (0, 64 * MiB + 256 * 1024),
+                (262143, 64 * MiB + 300 * 1024), (LONG_TOTAL - 16 * MiB - 1, 16 * MiB + 1),
+                (LONG_TOTAL - 1, 1)]
+
+
+@pytest.fixture(scope="module")
+def long_case(oracle_mod):
+    """96 MiB of splitmix bytes and the oracle's CRCs of every call of
+    test_long_buffers, computed once for both of its contexts."""
+    host = oracle_mod.splitmix_bytes(0x4C4F4E47, LONG_TOTAL)
+    rng = np.random.default_rng(64)
+    off = np.array([o for o, _ in LONG_BUFFERS], np.uint64)
+    ln = np.array([n for _, n in LONG_BUFFERS], np.uint64)
+    assert int((off + ln).max()) <= LONG_TOTAL
+    init = rng.integers(0, 2 ** 32, len(LONG_BUFFERS), dtype=np.uint64).astype(np.uint32)
+    want = {fin: oracle_mod.entries(host, off, ln, init=init, finalize=fin) for fin in (True, False)}
+    segs = {}
+    for name, shift, seg_bytes in (("planned", 5, 17 * MiB + 3), ("aligned", 0, 32 * MiB)):
+        so = shift + np.arange(2, dtype=np.uint64) * seg_bytes
+        sl = np.full(2, seg_bytes, np.uint64)
+        segs[name] = (shift, seg_bytes, init[:2],
+                      oracle_mod.entries(host, so, sl),
+                      oracle_mod.entries(host, so, sl, init=init[:2], finalize=False))
+    return host, off, ln, init, want, segs
+
+
+@pytest.mark.parametrize("ncu", [0, 1], ids=["all_cus", "ncu1"])
+def test_long_buffers(ramcrc, oracle_mod, long_case, ncu):
+    """Buffers past the sizes where the combine changes: more than 64 chunks
+    (a second pass of combine_one's lane loop: 65 to 259 chunks here) and
+    chunks 64 MiB or more in front of the end (the third factor of
+    xpow_blocks; the arithmetic is at LONG_BUFFERS), through the batch call with random initial states, raw and
+    finalized; ramcrc_segments_device with 17 MiB + 3 byte segments from an
+    odd base (the planned path, 69 chunks each) and 32 MiB segments from a
+    2 MiB-aligned base (the fast path: 2 * 64 chunk pairs are fewer than
+    2 * 16 * 256 waves, so the shift stays 18 and a segment has 128 chunks; at
+    one CU it is 20, 32 chunks).  On a default context and on one sized for a
+    single CU, where one workgroup's 16 waves take every chunk in turn."""
+    host, off, ln, init, want, segs = long_case
+    over = torch.empty(LONG_TOTAL + 2 * MiB, dtype=torch.uint8, device="cuda")
+    a = -over.data_ptr() % (2 * MiB)
+    base = over[a:a + LONG_TOTAL]
+    assert base.data_ptr() % (2 * MiB) == 0
+    base.copy_(torch.from_numpy(host))
+    c = ramcrc.Context(0)
+    try:
+        c.set_cus(ncu)
+        for fin in (True, False):
+            got = run_api(c, "batch", base, off, ln, init, fin)
+            bad = np.nonzero(got != want[fin])[0]
+            assert bad.size == 0, (fin, [LONG_BUFFERS[i] for i in bad])
+        for name, (shift, seg_bytes, sinit, w_fin, w_raw) in segs.items():
+            out = torch.zeros(2, dtype=torch.int32, device="cuda")
+            c.segments(base[shift:], seg_bytes, 2, out)
+            assert np.array_equal(u32(out), w_fin), name
+            c.segments(base[shift:], seg_bytes, 2, out, init=i32_from_u32(sinit), finalize=False)
+            assert np.array_equal(u32(out), w_raw), name
+        c.check()
+    finally:
+        c.close()
+
+
 def test_entries_config3_sample(ctx, oracle_mod):
     from ramcloud_amd import workloads
     lens = workloads.entry_lengths(60000)

@@ -16,13 +16,13 @@ from ramcloud_amd import segments
 
 import append_cases as ac
 import segment_cases
+from append_cases import PATTERN, Walked, _append, _launch, _u32
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 KiB = 1024
 MiB = 1 << 20
-PATTERN = 0x5A5A5A5A
 
 
 @pytest.fixture(scope="module")
@@ -31,67 +31,6 @@ def ctx(ramcrc):
     c = ramcrc.Context(0)
     yield c
     c.close()
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-class Walked:
-    """Source segments on the device with the walk's status and record table."""
-
-    def __init__(self, ctx, buf, certs, cap, nseg, min_entry=2, d_buf=None):
-        self.buf, self.cap, self.nseg = buf, cap, nseg
-        self.d = torch.from_numpy(buf).cuda() if d_buf is None else d_buf
-        dc = torch.from_numpy(np.ascontiguousarray(certs, np.uint32).view(np.int32)).cuda()
-        ecap = nseg * (cap // min_entry + 1)
-        self.d_status = torch.zeros((nseg, 4), dtype=torch.int32, device="cuda")
-        self.d_entries = torch.zeros((ecap, 4), dtype=torch.int32, device="cuda")
-        self.d_n = torch.zeros(1, dtype=torch.int64, device="cuda")
-        ctx.segment_walk(self.d, cap, cap, nseg, dc, self.d_status, self.d_entries, self.d_n)
-        ctx.check()
-        n = int(self.d_n.item())
-        assert n <= ecap
-        self.status = _u32(self.d_status)
-        self.table = np.ascontiguousarray(_u32(self.d_entries[:n]))
-
-
-def _launch(ctx, w, place, n_part, out_capacity, out_stride, place_cap=None, n_place=None):
-    place = np.ascontiguousarray(place, np.uint32).reshape(-1, 2)
-    pcap = place.shape[0] if place_cap is None else place_cap
-    d_place = torch.zeros((max(pcap, 1), 2), dtype=torch.int32, device="cuda")[:pcap]
-    if place.shape[0]:
-        d_place[:place.shape[0]] = torch.from_numpy(place.view(np.int32)).cuda()[:pcap]
-    d_np = torch.tensor([place.shape[0] if n_place is None else n_place], dtype=torch.int64,
-                        device="cuda")
-    n_out = w.nseg * n_part
-    out = torch.full((n_out * out_stride,), ac.FILL, dtype=torch.uint8, device="cuda")
-    certs = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
-    stat = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
-    ctx.recovery_append(w.d, w.cap, w.nseg, w.d_status, w.d_entries, w.d_n, d_place, d_np, n_part,
-                        out, out_stride, out_capacity, certs, stat)
-    return out, certs, stat
-
-
-def _append(ctx, ramcrc, oracle, w, place, n_part, out_capacity, out_stride=None, exp=None,
-            what=""):
-    """One device call checked against the expectation and the host form."""
-    if callable(place):
-        place = place(w.table)
-    place = np.ascontiguousarray(place, np.uint32).reshape(-1, 2)
-    out_stride = out_stride or (out_capacity + 15) // 16 * 16
-    d_out, d_certs, d_stat = _launch(ctx, w, place, n_part, out_capacity, out_stride)
-    ctx.check()
-    out, certs, stat = d_out.cpu().numpy(), _u32(d_certs), _u32(d_stat)
-    if exp is None:
-        exp = ac.expected(w.buf, w.cap, w.table, w.status, place, w.nseg, n_part, out_capacity)
-    ac.check_outputs(oracle, exp, out, out_stride, out_capacity, certs, stat, what)
-    h_out = np.full(out.size, ac.FILL, np.uint8)
-    h_certs, h_stat = ramcrc.recovery_append_host(w.buf, w.cap, w.nseg, w.status, w.table, place,
-                                                  n_part, h_out, out_stride, out_capacity)
-    assert np.array_equal(h_out, out), (what, "host and device outputs differ")
-    assert np.array_equal(h_certs, certs) and np.array_equal(h_stat, stat), what
-    return place, d_out, certs, stat
 
 
 def test_reference_goldens(ctx, ramcrc, oracle_mod, golden):
@@ -188,10 +127,14 @@ def test_bad_source(ctx, ramcrc, oracle_mod):
 
 
 @pytest.mark.parametrize("variant", ["decreasing", "record_at_n_entries", "partition_at_n_part",
-                                     "n_place_over_cap"])
+                                     "n_place_over_cap", "segment_at_n_seg", "second_run"])
 def test_refusals(ctx, ramcrc, oracle_mod, variant):
     """Case 7: RAMCRC_EREFUSED from check(), nothing written, and a following
-    valid call on the same context is correct."""
+    valid call on the same context is correct.  The last two damage the
+    device's record table, not the list: a placed record whose segment field
+    is n_seg, and placed records that visit segment 0, then 1, then 0 again
+    (the table's segments are not contiguous runs); the table is put back for
+    the valid call."""
     nseg, cap, n_part = 2, 64 * KiB, 3
     buf, certs = ac.small_mixed(oracle_mod, nseg, 71)
     w = Walked(ctx, buf, certs, cap, nseg)
@@ -199,14 +142,25 @@ def test_refusals(ctx, ramcrc, oracle_mod, variant):
     bad = good.copy()
     mid = bad.shape[0] // 2
     kw = {}
+    edited = None
     if variant == "decreasing":
         bad[mid, 0] = bad[mid - 1, 0] - 1
     elif variant == "record_at_n_entries":
         bad[-1, 0] = w.table.shape[0]
     elif variant == "partition_at_n_part":
         bad[mid, 1] = n_part
-    else:
+    elif variant == "n_place_over_cap":
         kw = dict(place_cap=bad.shape[0] - 1, n_place=bad.shape[0])
+    elif variant == "segment_at_n_seg":
+        edited = int(bad[mid, 0])
+        w.d_entries[edited, 0] = nseg
+    else:
+        # (the walk fixes no order across segments: the first run's segment,
+        # 0 or 1, is the one that comes back at the end of the list)
+        edited = int(bad[-1, 0])
+        first, last = int(w.table[bad[0, 0], 0]), int(w.table[edited, 0])
+        assert first != last and bad[-2, 0] != edited and w.table[bad[-2, 0], 0] == last
+        w.d_entries[edited, 0] = first
     d_out, d_certs, d_stat = _launch(ctx, w, bad, n_part, cap, cap, **kw)
     with pytest.raises(ramcrc.RamcrcError) as e:
         ctx.check()
@@ -214,7 +168,72 @@ def test_refusals(ctx, ramcrc, oracle_mod, variant):
     assert bool((d_out == ac.FILL).all())
     assert (_u32(d_certs) == PATTERN).all() and (_u32(d_stat) == PATTERN).all()
     ctx.check()   # the refusal was taken
+    if edited is not None:
+        w.d_entries[edited, 0] = int(w.table[edited, 0])
     _append(ctx, ramcrc, oracle_mod, w, good, n_part, cap)
+
+
+@pytest.mark.parametrize("damage", ["overlong_flag", "payload_past_stride"])
+def test_record_that_never_fits(ctx, ramcrc, oracle_mod, damage):
+    """A mid-run record of a real walk table flagged RAMCRC_SEG_ENTRY_OVERLONG,
+    or with a length edited so that its payload runs past seg_stride (the same
+    edit in the device table and the copy read back), placed in partition 0
+    with later records behind it: it never fits (include/ramcrc.h), so that
+    output is APPEND_FULL with only the records before it, and the other
+    partitions and the other segment get everything placed in them."""
+    nseg, cap, n_part = 2, 64 * KiB, 3
+    buf, certs = ac.small_mixed(oracle_mod, nseg, 75)
+    w = Walked(ctx, buf, certs, cap, nseg)
+    n = w.table.shape[0]
+    seg = int(w.table[0, 0])                      # the segment whose run comes first
+    n0 = int((w.table[:, 0] == seg).sum())
+    assert (w.table[:n0, 0] == seg).all()
+    rec = n0 // 2 // n_part * n_part              # placed in partition 0
+    assert 0 < rec < n0 - n_part
+    ac.damage_record(w.table, rec, damage, cap)
+    w.d_entries[rec] = torch.from_numpy(w.table[rec].view(np.int32)).cuda()
+    place = [(r, r % n_part) for r in range(n)]
+    _, _, _, stat = _append(ctx, ramcrc, oracle_mod, w, place, n_part, cap)
+    k = seg * n_part
+    assert stat[k].tolist() == [segments.SEG_APPEND_FULL, rec // n_part]
+    assert stat[k + 1].tolist() == [segments.SEG_OK, len(range(1, n0, n_part))]
+    assert stat[k + 2].tolist() == [segments.SEG_OK, len(range(2, n0, n_part))]
+    rest = np.delete(stat, [k, k + 1, k + 2], axis=0)
+    assert (rest[:, 0] == segments.SEG_OK).all() and rest[:, 1].sum() == n - n0
+
+
+def test_unaligned_outputs(ctx, ramcrc, oracle_mod, aligned):
+    """"d_out and out_stride are free" (include/ramcrc.h): case 3 again with
+    d_out three bytes into its allocation and out_stride = out_capacity + 7,
+    so every output starts at another residue mod 16.  The three bytes before
+    d_out and every stride gap keep the fill (check_outputs looks at each
+    whole stride past the head), and the host form gives the same bytes."""
+    w, n_part, lead = aligned, 3, 3
+    out_capacity = w.cap
+    out_stride = out_capacity + 7
+    place = ac.alignment_placements(w.table, n_part)
+    d_place = torch.from_numpy(place.view(np.int32)).cuda()
+    d_np = torch.tensor([place.shape[0]], dtype=torch.int64, device="cuda")
+    n_out = w.nseg * n_part
+    whole = torch.full((lead + n_out * out_stride,), ac.FILL, dtype=torch.uint8, device="cuda")
+    d_out = whole[lead:]
+    assert d_out.data_ptr() % 16 == lead
+    d_certs = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
+    d_stat = torch.full((n_out, 2), PATTERN, dtype=torch.int32, device="cuda")
+    ctx.recovery_append(w.d, w.cap, w.nseg, w.d_status, w.d_entries, w.d_n, d_place, d_np, n_part,
+                        d_out, out_stride, out_capacity, d_certs, d_stat)
+    ctx.check()
+    got = whole.cpu().numpy()
+    assert (got[:lead] == ac.FILL).all()
+    out, certs, stat = got[lead:], _u32(d_certs), _u32(d_stat)
+    exp = ac.expected(w.buf, w.cap, w.table, w.status, place, w.nseg, n_part, out_capacity)
+    ac.check_outputs(oracle_mod, exp, out, out_stride, out_capacity, certs, stat)
+    assert (stat[:, 0] == segments.SEG_OK).all() and stat[:, 1].sum() == place.shape[0]
+    h_out = np.full(out.size, ac.FILL, np.uint8)
+    h_certs, h_stat = ramcrc.recovery_append_host(w.buf, w.cap, w.nseg, w.status, w.table, place,
+                                                  n_part, h_out, out_stride, out_capacity)
+    assert np.array_equal(h_out, out)
+    assert np.array_equal(h_certs, certs) and np.array_equal(h_stat, stat)
 
 
 def test_one_context_changing_shapes(ctx, ramcrc, oracle_mod, mixed, aligned):

@@ -16,8 +16,10 @@ KiB = 1024
 
 
 def _run(ramcrc, oracle, buf, certs, cap, nseg, place, n_part, out_capacity, out_stride=None,
-         what=""):
+         what="", edit=None):
     status, table = ac.host_walk(oracle, buf, certs, nseg, cap)
+    if edit is not None:
+        edit(table)   # a hand-edited record, as a caller's own table may hold
     if callable(place):
         place = place(table)
     place = np.ascontiguousarray(place, np.uint32).reshape(-1, 2)
@@ -106,28 +108,69 @@ def test_bad_source(ramcrc, oracle_mod):
         assert stat[s * n_part:(s + 1) * n_part, 1].sum() > 0
 
 
-@pytest.mark.parametrize("variant", ["decreasing", "record_at_n_entries", "partition_at_n_part"])
+@pytest.mark.parametrize("variant", ["decreasing", "record_at_n_entries", "partition_at_n_part",
+                                     "segment_at_n_seg", "second_run"])
 def test_refusals(ramcrc, oracle_mod, variant):
     """Case 7 (the host form takes a plain count, so it has no n_place >
-    place_cap variant): EINVAL, nothing written, and a valid call after it."""
+    place_cap variant): EINVAL, nothing written, and a valid call after it.
+    The last two damage the table, not the list: a placed record whose segment
+    field is n_seg, and placed records that visit segment 0, then 1, then 0
+    again (the device form refuses a table whose segments are not contiguous
+    runs)."""
     nseg, cap, n_part = 2, 64 * KiB, 3
     buf, certs = ac.small_mixed(oracle_mod, nseg, 71)
     status, table = ac.host_walk(oracle_mod, buf, certs, nseg, cap)
     good = ac.mixed_placements(table, n_part, 9)
     bad = good.copy()
+    bad_table = table.copy()
     mid = bad.shape[0] // 2
     if variant == "decreasing":
         bad[mid, 0] = bad[mid - 1, 0] - 1
     elif variant == "record_at_n_entries":
         bad[-1, 0] = table.shape[0]
-    else:
+    elif variant == "partition_at_n_part":
         bad[mid, 1] = n_part
+    elif variant == "segment_at_n_seg":
+        bad_table[bad[mid, 0], 0] = nseg
+    else:
+        assert table[bad[0, 0], 0] == 0 and table[bad[-1, 0], 0] == 1
+        assert bad[-2, 0] != bad[-1, 0] and table[bad[-2, 0], 0] == 1
+        bad_table[bad[-1, 0], 0] = 0
     out = np.full(nseg * n_part * cap, ac.FILL, np.uint8)
     with pytest.raises(ramcrc.RamcrcError) as e:
-        ramcrc.recovery_append_host(buf, cap, nseg, status, table, bad, n_part, out, cap, cap)
+        ramcrc.recovery_append_host(buf, cap, nseg, status, bad_table, bad, n_part, out, cap, cap)
     assert e.value.code == ramcrc.EINVAL
     assert (out == ac.FILL).all()
     _run(ramcrc, oracle_mod, buf, certs, cap, nseg, good, n_part, cap)
+
+
+@pytest.mark.parametrize("damage", ["overlong_flag", "payload_past_stride"])
+def test_record_that_never_fits(ramcrc, oracle_mod, damage):
+    """A mid-run record flagged RAMCRC_SEG_ENTRY_OVERLONG, or whose length was
+    edited so that its payload runs past seg_stride, placed in partition 0 of
+    segment 0 with later records behind it: it "never fits" (include/ramcrc.h),
+    so that output is APPEND_FULL and holds only the records before it, while
+    the other partitions and the other segment get everything placed in them
+    (_run checks the bytes against append_cases.expected)."""
+    nseg, cap, n_part = 2, 64 * KiB, 3
+    buf, certs = ac.small_mixed(oracle_mod, nseg, 75)
+    where = {}
+
+    def edit(table):
+        n0 = int((table[:, 0] == 0).sum())
+        rec = n0 // 2 // n_part * n_part   # placed in partition 0
+        assert 0 < rec < n0 - n_part
+        ac.damage_record(table, rec, damage, cap)
+        where["rec"], where["n0"] = rec, n0
+
+    place = lambda t: [(r, r % n_part) for r in range(t.shape[0])]
+    table, place, _, _, stat = _run(ramcrc, oracle_mod, buf, certs, cap, nseg, place, n_part, cap,
+                                    edit=edit)
+    rec, n0, n = where["rec"], where["n0"], table.shape[0]
+    assert stat[0].tolist() == [segments.SEG_APPEND_FULL, rec // n_part]
+    assert stat[1].tolist() == [segments.SEG_OK, len(range(1, n0, n_part))]
+    assert stat[2].tolist() == [segments.SEG_OK, len(range(2, n0, n_part))]
+    assert (stat[n_part:, 0] == segments.SEG_OK).all() and stat[n_part:, 1].sum() == n - n0
 
 
 def test_argument_checks(ramcrc, oracle_mod):
