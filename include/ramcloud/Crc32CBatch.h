@@ -181,6 +181,36 @@ class Crc32CBatch {
     }
 
     /**
+     * The placement decision of RecoverySegmentBuilder::build
+     * (src/RecoverySegmentBuilder.cc:74-201) for the records a
+     * deviceReplayVerify (or a walk) left in HBM: Key::getHash, whichPartition
+     * over d_tablets (the RecoveryPartition's tablets in list order, partition =
+     * user_data) and isEntryAlive.  Writes the {record, partition} list and its
+     * length to d_place / d_nPlace, which deviceRecoveryAppend takes as they
+     * are, the per-replica flags and counters to d_partStatus and, when
+     * d_keyHash is not NULL, every record's key hash: see
+     * ramcrc_recovery_partition_device.  Returns after the kernels finished on
+     * `stream`; throws when the call was refused (a tablet's partition >=
+     * partitions, a record table that is not a walk's).
+     */
+    void
+    deviceRecoveryPartition(const void* d_base, uint64_t stride, uint64_t count,
+                            const ramcrc_seg_status* d_status, const ramcrc_seg_entry* d_entries,
+                            uint64_t entriesCap, const uint64_t* d_nEntries,
+                            const ramcrc_tablet* d_tablets, uint32_t tablets, uint32_t partitions,
+                            ramcrc_placement* d_place, uint64_t placeCap, uint64_t* d_nPlace,
+                            uint64_t* d_keyHash, ramcrc_partition_status* d_partStatus,
+                            void* stream = NULL)
+    {
+        check(ramcrc_recovery_partition_device(context(), d_base, stride, count, d_status,
+                                               d_entries, entriesCap, d_nEntries, d_tablets,
+                                               tablets, partitions, d_place, placeCap, d_nPlace,
+                                               d_keyHash, d_partStatus, stream),
+              "ramcrc_recovery_partition_device");
+        sync(stream);
+    }
+
+    /**
      * Object::assembleForLog's checksum for a batch of serialized objects
      * (the write path, src/ObjectManager.cc:1274): header.checksum of every
      * object (Object::Header + keysAndValue, src/Object.h:137-182) is set to

@@ -39,8 +39,9 @@ enum {
     RAMCRC_ENODEV = -4,   /* no usable gfx950 device */
     RAMCRC_ERCCL = -5,    /* RCCL failure or RCCL unavailable (multi-GPU shard) */
     RAMCRC_EREFUSED = -6, /* a launch found more chunks than the context's scratch holds, or
-                             ramcrc_recovery_append_device a placement list it refuses, and
-                             wrote none of its outputs (see ramcrc_ctx_check) */
+                             ramcrc_recovery_append_device a placement list it refuses, or
+                             ramcrc_recovery_partition_device a tablet list or record table
+                             it refuses, and wrote none of its outputs (see ramcrc_ctx_check) */
     RAMCRC_EINTERNAL = -7, /* a small-entry launch found its bin layout inconsistent with the
                              entries it binned and wrote none of its small-entry outputs.
                              Only a corrupted bin table produces it (the TEST_DIRTY_BINS
@@ -314,6 +315,133 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
                                 uint32_t out_capacity, ramcrc_seg_cert* out_certs,
                                 ramcrc_append_status* out_status);
 
+/* The placement decision of RecoverySegmentBuilder::build
+ * (src/RecoverySegmentBuilder.cc:74-201): for every walked record the key hash
+ * (Key::getHash, src/Key.cc:140-151: MurmurHash3 x64-128 of the key, seeded
+ * with the low 32 bits of the table id, first output word), the tablet lookup
+ * (whichPartition, :330-343) and the liveness test (isEntryAlive, :300-307).
+ * It writes the {record, partition} list ramcrc_recovery_append_device takes,
+ * so walk -> partition -> append builds sealed recovery segments from replicas
+ * in device memory without a host round trip. */
+#define RAMCRC_LOG_ENTRY_TYPE_SEGHEADER 1u   /* LOG_ENTRY_TYPE_SEGHEADER, src/LogEntryTypes.h:32 */
+#define RAMCRC_LOG_ENTRY_TYPE_RPCRESULT 7u   /* LOG_ENTRY_TYPE_RPCRESULT, src/LogEntryTypes.h:50 */
+
+typedef struct ramcrc_tablet {      /* one ProtoBuf::Tablets::Tablet of the RecoveryPartition */
+    uint64_t table_id;
+    uint64_t start_key_hash;        /* inclusive */
+    uint64_t end_key_hash;          /* inclusive */
+    uint64_t ctime_segment_id;      /* ctime_log_head_id */
+    uint32_t ctime_offset;          /* ctime_log_head_offset */
+    uint32_t partition;             /* user_data; must be < n_part */
+} ramcrc_tablet;
+
+typedef struct ramcrc_partition_status {   /* per source segment */
+    uint32_t flags;      /* RAMCRC_SEG_OK | RAMCRC_SEG_SOURCE_BAD | RAMCRC_SEG_NO_HEADER | RAMCRC_SEG_MALFORMED */
+    uint32_t placed;     /* placements emitted */
+    uint32_t unplaced;   /* records with no tablet ("Couldn't place object") */
+    uint32_t dead;       /* records dropped by isEntryAlive */
+} ramcrc_partition_status;
+
+#define RAMCRC_SEG_NO_HEADER 512u    /* a record build would place has no usable SEGHEADER before
+                                        it (build DIEs there): the segment places nothing */
+#define RAMCRC_SEG_MALFORMED 1024u   /* some record is too short for its type's fields (our
+                                        rule, below); that record is not placed */
+
+/* Source segment s (d_base + s * seg_stride) is handled in the order of its
+ * records in the walk's table (d_status, d_entries, *d_n_entries: a walk's
+ * outputs; min(*d_n_entries, entries_cap) records are read).  d_part_status[s]
+ * is RAMCRC_SEG_OK plus RAMCRC_SEG_MALFORMED when it applies, or:
+ *   RAMCRC_SEG_SOURCE_BAD  d_status[s] lacks RAMCRC_SEG_OK (RAMCRC_SEG_TABLE_FULL
+ *                          included): build throws before its loop.  Nothing is
+ *                          placed or counted, the records' hashes read 0;
+ *   RAMCRC_SEG_NO_HEADER   a record of a placed type (below) has no SEGHEADER
+ *                          record before it in the segment, or the latest one
+ *                          before it is shorter than the 20 bytes that hold its
+ *                          segmentId (or not readable: RAMCRC_SEG_ENTRY_OVERLONG, a
+ *                          payload past seg_stride).  Nothing is placed, and
+ *                          placed, unplaced and dead read 0 (MALFORMED may be
+ *                          set beside it; the hashes are still written).
+ * The log position of a record is {the u64 at payload byte 8 of the latest
+ * SEGHEADER record before it in its segment (SegmentHeader::segmentId,
+ * src/LogMetadata.h:51-61), the record's offset}.
+ *
+ * Per record, by type (offsets are payload-relative; other types -- SEGHEADER,
+ * LOGDIGEST, TABLESTATS, INVALID, unknown ones -- place nothing):
+ *   SAFEVERSION  one placement for each partition 0 .. n_part-1, ascending; no
+ *                tablet lookup, no liveness test (:101-116);
+ *   TXPLIST      count = u32 at 16, participants {tableId, keyHash, rpcId} of
+ *                24 bytes each from byte 24 (src/ParticipantList.h:81-112): in
+ *                participant order one placement per participant whose tablet
+ *                is found (the same partition may repeat); no liveness test
+ *                (:118-141);
+ *   OBJ          tableId = u64 at 16, numKeys = u8 at 24, the first key's
+ *                length = u16 at 25 (cumulativeLengths[0]), its bytes from
+ *                25 + 2 * numKeys (src/Object.h:40-45,137-181); numKeys 0 or
+ *                length 0 hashes the empty key;
+ *   PREP         the same 32 bytes further on (src/PreparedOp.h:63-94);
+ *   OBJTOMB      tableId = u64 at 0, key = [32, length) (src/Object.h:285-336);
+ *   RPCRESULT, PREPTOMB, TXDECISION   tableId = u64 at 0, the stored keyHash =
+ *                u64 at 8 (src/RpcResult.h:75-126, src/PreparedOp.h:142-182,
+ *                src/TxDecisionRecord.h:62-138).
+ * The last six place at most once: whichPartition picks the first tablet in
+ * list order with table_id equal and start_key_hash <= hash <= end_key_hash
+ * (unsigned; tablets may overlap); none found counts in `unplaced`.  Then the
+ * record is alive when its position >= {ctime_segment_id, ctime_offset} of
+ * that tablet (segment id first, then offset), else it counts in `dead`.  An
+ * alive record gets one placement {record, tablet.partition}.
+ *
+ * Malformed records (the reference's behaviour there is undefined; this rule
+ * is this library's): a record of a placed type that carries
+ * RAMCRC_SEG_ENTRY_OVERLONG or whose payload runs past seg_stride; an OBJ / PREP
+ * shorter than 25 / 57 bytes, or with numKeys > 0 and shorter than the u16 key
+ * length or the end of the first key; an OBJTOMB shorter than 32 bytes; an
+ * RPCRESULT, PREPTOMB or TXDECISION shorter than 16; a TXPLIST shorter than its
+ * 24-byte header or than 24 + 24 * count.  Such a record is not placed, counts
+ * nowhere, its hash reads 0, and its segment gets RAMCRC_SEG_MALFORMED.
+ *
+ * d_key_hash (nullable, one slot per record read) receives the computed or
+ * stored hash of every OBJ, PREP, OBJTOMB, RPCRESULT, PREPTOMB and TXDECISION
+ * record of a segment with RAMCRC_SEG_OK, and 0 for every other record.
+ *
+ * The list goes to d_place in record order (it does not decrease in `record`)
+ * and its length to *d_n_place (device), as ramcrc_recovery_append_device
+ * reads them.  When more than place_cap placements are needed, *d_n_place
+ * still receives the needed count, only the first place_cap are written, and
+ * this call does not refuse: the append does, by its own *d_n_place >
+ * place_cap rule.  Slots of d_place at or past the list's end are not written.
+ *
+ * The call refuses -- *d_n_place = 0 is its only output, and ramcrc_ctx_check
+ * returns RAMCRC_EREFUSED -- when n_part is 0, a tablet names a partition >=
+ * n_part, a record a segment >= n_seg, or the table's segments are not
+ * contiguous runs.
+ *
+ * d_base 16-byte aligned, seg_stride a multiple of 16 (the walk's rules);
+ * n_seg, entries_cap, place_cap < 2^32.  Up to 256 tablets are staged in LDS;
+ * longer lists are read from device memory in the same order.  Scratch comes
+ * from the context: after ramcrc_ctx_reserve(ctx, 16 + 9 * n_seg,
+ * entries_cap), or after one call of the same shape, it does not allocate.
+ * Stream-ordered, asynchronous. */
+int ramcrc_recovery_partition_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
+                                     uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                     const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                     const uint64_t* d_n_entries, const ramcrc_tablet* d_tablets,
+                                     uint32_t n_tablets, uint32_t n_part,
+                                     ramcrc_placement* d_place, uint64_t place_cap,
+                                     uint64_t* d_n_place, uint64_t* d_key_hash,
+                                     ramcrc_partition_status* d_part_status, void* stream);
+
+/* The same on the host, single-threaded: host pointers, n_entries records,
+ * *n_place receives the needed count (at most place_cap placements are
+ * written).  Returns RAMCRC_EINVAL where the device form refuses (nothing is
+ * written).  No alignment rules. */
+int ramcrc_recovery_partition_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                                   const ramcrc_seg_status* status,
+                                   const ramcrc_seg_entry* entries, uint64_t n_entries,
+                                   const ramcrc_tablet* tablets, uint32_t n_tablets,
+                                   uint32_t n_part, ramcrc_placement* place, uint64_t place_cap,
+                                   uint64_t* n_place, uint64_t* key_hash,
+                                   ramcrc_partition_status* part_status);
+
 /* ObjectManager::replaySegment's checksum checks for every record of a walk
  * whose segment passed the metadata check (d_status flags RAMCRC_SEG_OK;
  * records of failed segments are skipped, as RecoverySegmentBuilder::build
@@ -585,7 +713,9 @@ int ramcrc_ctx_status(ramcrc_ctx* ctx, uint32_t* status);
  * overlap or total more bytes than the device holds (ramcrc_batch_device,
  * ramcrc_verify_objects_device, ramcrc_assemble_objects_device); raise
  * ramcrc_ctx_reserve and retry.  ramcrc_recovery_append_device refuses a
- * placement list that breaks its rules: correct the list.  The host entry points (ramcrc_batch_host,
+ * placement list that breaks its rules: correct the list;
+ * ramcrc_recovery_partition_device a tablet whose partition is out of range
+ * or a record table that is not a walk's.  The host entry points (ramcrc_batch_host,
  * ramcrc_assemble_objects_host) check by themselves. */
 int ramcrc_ctx_check(ramcrc_ctx* ctx, void* stream);
 

@@ -20,11 +20,11 @@ LIB = os.path.join(LIBDIR, "libramcrc.so")
 ARCH = "gfx950"
 
 SOURCES = ["ramcrc_device.hip", "ramcrc_host.cc", "ramcrc_shard.hip", "ramcrc_fill.hip"]
-HEADERS = ["gf2.h", "walk_rules.h", "shard_plan.h",
+HEADERS = ["gf2.h", "walk_rules.h", "shard_plan.h", "murmur3.h", "partition_rules.h",
            # parts of ramcrc_device.hip (one translation unit)
            "dev_common.inc", "dev_chunks.inc", "dev_bins.inc", "dev_entries.inc",
            "dev_plan.inc", "dev_host.inc", "dev_walk.inc", "dev_checks.inc",
-           "dev_append.inc"]
+           "dev_append.inc", "dev_partition.inc"]
 
 
 def hipcc():

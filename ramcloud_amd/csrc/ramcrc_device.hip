@@ -54,6 +54,7 @@
 //   dev_walk.inc     k_seg_walk and the parallel walk (k_walk_*)
 //   dev_checks.inc   k_obj_compare, k_obj_stamp, certificate kernels
 //   dev_append.inc   k_app_mark, k_app_scan, k_app_copy (recovery-segment append)
+//   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -69,6 +70,8 @@
 
 #include "gf2.h"
 #include "walk_rules.h"
+#include "murmur3.h"
+#include "partition_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -88,6 +91,7 @@ using ramcrc::OpTable;
 #include "dev_walk.inc"
 #include "dev_checks.inc"
 #include "dev_append.inc"
+#include "dev_partition.inc"
 
 extern "C" {
 
@@ -1006,6 +1010,88 @@ int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t se
         hipLaunchKernelGGL(k_app_copy, dim3(uint32_t(gc)), dim3(kAppCopyThreads), 0, s, a);
         HIPCHK(hipGetLastError());
     }
+    return RAMCRC_OK;
+}
+
+int ramcrc_recovery_partition_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
+                                     uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                     const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                     const uint64_t* d_n_entries, const ramcrc_tablet* d_tablets,
+                                     uint32_t n_tablets, uint32_t n_part,
+                                     ramcrc_placement* d_place, uint64_t place_cap,
+                                     uint64_t* d_n_place, uint64_t* d_key_hash,
+                                     ramcrc_partition_status* d_part_status, void* stream)
+{
+    if (!c || n_seg >= 0xFFFFFFFFull || entries_cap >= 0xFFFFFFFFull || place_cap >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (!d_n_place || !d_n_entries || (n_seg && (!d_base || !d_status || !d_part_status)) ||
+        (entries_cap && !d_entries) || (place_cap && !d_place) || (n_tablets && !d_tablets))
+        return RAMCRC_EINVAL;
+    const uint64_t B = reinterpret_cast<uint64_t>(d_base);
+    if ((B & 15) || (seg_stride & 15) || (seg_stride && n_seg > UINT64_MAX / seg_stride))
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch words in the chunk-partial buffer: the refusal word, then nine
+    // words per segment (runs, headers, flags, counters); the records' counts
+    // in the plan buffer and the tile sums in the group prefixes (ramcrc.h
+    // states these sizes)
+    const uint64_t head_words = 4 + 9 * n_seg;
+    int rc = reserve_locked(c, head_words, entries_cap);
+    if (rc)
+        return rc;
+    PartDesc a{};
+    a.base = B;
+    a.stride = seg_stride;
+    a.nseg = n_seg;
+    a.status = d_status;
+    a.entries = reinterpret_cast<const u32x4*>(d_entries);
+    a.ecap = entries_cap;
+    a.n_entries = d_n_entries;
+    a.tablets = d_tablets;
+    a.ntab = n_tablets;
+    a.npart = n_part;
+    a.place = reinterpret_cast<uint2*>(d_place);
+    a.pcap = place_cap;
+    a.n_place = d_n_place;
+    a.key_hash = d_key_hash;
+    a.pstat = d_part_status;
+    a.refuse = c->partials;
+    a.run_lo = c->partials + 4;
+    a.run_hi = a.run_lo + n_seg;
+    a.run_cnt = a.run_hi + n_seg;
+    a.hdr_cnt = a.run_cnt + n_seg;
+    a.hdr_first = a.hdr_cnt + n_seg;
+    a.sflags = a.hdr_first + n_seg;
+    a.counts = a.sflags + n_seg;
+    a.cls = c->plan_local;
+    a.tile_sum = c->group_pref;
+    a.ctx_status = c->status;
+    HIPCHK(hipMemsetAsync(c->partials, 0, head_words * sizeof(uint32_t), s));
+    const uint64_t cap_grid = uint64_t(8) * c->ncu;
+    auto grid_of = [&](uint64_t items, uint64_t per) {
+        uint64_t gr = (items + per - 1) / per;
+        return dim3(uint32_t(gr < 1 ? 1 : (gr > cap_grid ? cap_grid : gr)));
+    };
+    const uint64_t heads_items = entries_cap > n_tablets ? entries_cap : n_tablets;
+    hipLaunchKernelGGL(k_part_heads, grid_of(heads_items, kPartThreads), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (n_tablets <= kPartLdsTablets)
+        hipLaunchKernelGGL(k_part_classify<true>, grid_of(entries_cap, kPartThreads),
+                           dim3(kPartThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_part_classify<false>, grid_of(entries_cap, kPartThreads),
+                           dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_part_void, grid_of(n_seg, 1), dim3(kWaveSize), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_part_tiles, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_part_emit, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }
 

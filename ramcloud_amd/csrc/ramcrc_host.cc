@@ -19,6 +19,8 @@
 #include <string.h>
 
 #include "gf2.h"
+#include "murmur3.h"
+#include "partition_rules.h"
 
 namespace {
 
@@ -302,6 +304,151 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
             lenle[b] = uint8_t(out_certs[k].segment_length >> (8 * b));
         out_certs[k].checksum = ~ramcrc_update(out_certs[k].checksum, lenle, 4);
     }
+    return RAMCRC_OK;
+}
+
+// RecoverySegmentBuilder::build's placement decision on the host: one pass
+// over the table in record order, the rules of partition_rules.h.
+int ramcrc_recovery_partition_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                                   const ramcrc_seg_status* status,
+                                   const ramcrc_seg_entry* entries, uint64_t n_entries,
+                                   const ramcrc_tablet* tablets, uint32_t n_tablets,
+                                   uint32_t n_part, ramcrc_placement* place, uint64_t place_cap,
+                                   uint64_t* n_place, uint64_t* key_hash,
+                                   ramcrc_partition_status* part_status)
+{
+    namespace rp = ramcrc_part;
+    if (n_part == 0 || n_seg >= 0xFFFFFFFFull || n_entries >= 0xFFFFFFFFull ||
+        place_cap >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (!n_place || (n_seg && (!base || !status || !part_status)) || (n_entries && !entries) ||
+        (place_cap && !place) || (n_tablets && !tablets))
+        return RAMCRC_EINVAL;
+    if (seg_stride && n_seg > UINT64_MAX / seg_stride)
+        return RAMCRC_EINVAL;
+    for (uint32_t t = 0; t < n_tablets; t++)
+        if (tablets[t].partition >= n_part)
+            return RAMCRC_EINVAL;
+    if (n_entries) {
+        // every segment's records are one run of the table, as k_part_heads demands
+        uint8_t* const seen = static_cast<uint8_t*>(calloc((n_seg + 7) / 8 + 1, 1));
+        if (!seen)
+            return RAMCRC_ENOMEM;
+        bool ok = true;
+        for (uint64_t i = 0; i < n_entries && ok; i++) {
+            const uint32_t seg = entries[i].segment;
+            ok = seg < n_seg;
+            if (ok && (!i || entries[i - 1].segment != seg)) {
+                ok = !(seen[seg >> 3] & (1u << (seg & 7)));
+                seen[seg >> 3] |= uint8_t(1u << (seg & 7));
+            }
+        }
+        free(seen);
+        if (!ok)
+            return RAMCRC_EINVAL;
+    }
+    struct Rd {
+        const uint8_t* pay;
+        uint32_t u8(uint32_t o) const { return pay[o]; }
+        uint32_t u16(uint32_t o) const { return ld16(pay + o); }
+        uint32_t u32(uint32_t o) const { return ld32(pay + o); }
+        uint64_t u64(uint32_t o) const { return ld64(pay + o); }
+    };
+    const auto tab = [&](uint32_t t) -> const ramcrc_tablet& { return tablets[t]; };
+    const uint8_t* const b = static_cast<const uint8_t*>(base);
+    for (uint64_t s = 0; s < n_seg; s++)
+        part_status[s] = ramcrc_partition_status{
+            (status[s].flags & RAMCRC_SEG_OK) ? RAMCRC_SEG_OK : RAMCRC_SEG_SOURCE_BAD, 0u, 0u, 0u};
+    uint64_t np = 0;
+    for (uint64_t i = 0; i < n_entries;) {
+        const uint32_t seg = entries[i].segment;
+        ramcrc_partition_status& st = part_status[seg];
+        bool have = false;   // a usable SEGHEADER before the record
+        uint64_t seg_id = 0;
+        // build DIEs at a placed record without a header: such a segment
+        // places nothing, so this is settled before anything is written
+        bool no_header = false;
+        for (uint64_t j = i; j < n_entries && entries[j].segment == seg && !no_header &&
+                             (status[seg].flags & RAMCRC_SEG_OK); j++) {
+            const ramcrc_seg_entry& r = entries[j];
+            const uint64_t pay = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+            const bool readable = !(r.header & RAMCRC_SEG_ENTRY_OVERLONG) && pay + r.length <= seg_stride;
+            if ((r.header & 0x3f) == RAMCRC_LOG_ENTRY_TYPE_SEGHEADER) {
+                have = readable && r.length >= rp::kSegHeaderBytes;
+                continue;
+            }
+            const uint32_t kind =
+                rp::parse(r.header & 0x3f, r.length, readable, Rd{b + seg * seg_stride + pay}).kind;
+            no_header = !have && kind != rp::kIgnored && kind != rp::kMalformed;
+        }
+        have = false;
+        const auto emit = [&](uint64_t rec, uint32_t part) {
+            if (no_header)
+                return;
+            if (np < place_cap)
+                place[np] = ramcrc_placement{uint32_t(rec), part};
+            np++;
+        };
+        for (; i < n_entries && entries[i].segment == seg; i++) {
+            const ramcrc_seg_entry& r = entries[i];
+            const uint32_t type = r.header & 0x3f;
+            const uint64_t pay = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+            const bool readable = !(r.header & RAMCRC_SEG_ENTRY_OVERLONG) && pay + r.length <= seg_stride;
+            if (key_hash)
+                key_hash[i] = 0;
+            if (type == RAMCRC_LOG_ENTRY_TYPE_SEGHEADER) {
+                have = readable && r.length >= rp::kSegHeaderBytes;
+                if (have)
+                    seg_id = ld64(b + seg * seg_stride + pay + rp::kSegIdAt);
+                continue;
+            }
+            if (!(status[seg].flags & RAMCRC_SEG_OK))
+                continue;
+            const Rd rd{b + seg * seg_stride + pay};
+            const rp::Parsed p = rp::parse(type, r.length, readable, rd);
+            if (p.kind == rp::kIgnored)
+                continue;
+            if (p.kind == rp::kMalformed) {
+                st.flags |= RAMCRC_SEG_MALFORMED;
+                continue;
+            }
+            if (p.kind == rp::kSafeVersion) {
+                for (uint32_t q = 0; q < n_part; q++)
+                    emit(i, q);
+                st.placed += n_part;
+            } else if (p.kind == rp::kPlist) {
+                for (uint32_t q = 0; q < p.count; q++) {
+                    const uint32_t o = rp::kPlistHeader + rp::kPartyBytes * q;
+                    const uint32_t t = rp::which_tablet(rd.u64(o), rd.u64(o + 8), n_tablets, tab);
+                    if (t != rp::kNoTablet) {
+                        emit(i, tablets[t].partition);
+                        st.placed++;
+                    }
+                }
+            } else {
+                const uint64_t hash = p.kind == rp::kKeyed
+                                          ? ramcrc::key_hash(p.table_id, rd.pay + p.key_off, p.key_len)
+                                          : p.hash;
+                if (key_hash)
+                    key_hash[i] = hash;
+                const uint32_t t = rp::which_tablet(p.table_id, hash, n_tablets, tab);
+                if (t == rp::kNoTablet) {
+                    st.unplaced++;
+                } else if (!have) {
+                    // (counted nowhere: the segment places nothing)
+                } else if (!rp::alive(seg_id, r.offset, tablets[t])) {
+                    st.dead++;
+                } else {
+                    emit(i, tablets[t].partition);
+                    st.placed++;
+                }
+            }
+        }
+        if (no_header)
+            st = ramcrc_partition_status{RAMCRC_SEG_NO_HEADER | (st.flags & RAMCRC_SEG_MALFORMED), 0u,
+                                         0u, 0u};
+    }
+    *n_place = np;
     return RAMCRC_OK;
 }
 

@@ -92,6 +92,10 @@ def lib():
                                                 vp, u64, u32, vp, vp, vp]),
         "ramcrc_recovery_append_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u64, u32, vp, u64, u32,
                                               vp, vp]),
+        "ramcrc_recovery_partition_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u32, u32,
+                                                   vp, u64, vp, vp, vp, vp]),
+        "ramcrc_recovery_partition_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u32, u32, vp, u64,
+                                                 _c.POINTER(u64), vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -256,6 +260,44 @@ def recovery_append_host(segments, seg_stride, n_seg, status, entries, place, n_
                                            p(out), out_stride, out_capacity, p(certs), p(ostat))
     _check(rc, "ramcrc_recovery_append_host")
     return certs, ostat
+
+
+def recovery_partition_host(segments, seg_stride, n_seg, status, entries, tablets, n_part,
+                            place_cap=None):
+    """RecoverySegmentBuilder::build's placement decision on the host
+    (ramcrc_recovery_partition_host).  segments uint8; status uint32 [n_seg, 4];
+    entries uint32 [n, 4]; tablets segments.TABLET_DTYPE [t].  place_cap: the
+    list's capacity (None: sized to the need).  Returns (place uint32 [m, 2]
+    with m = min(needed, place_cap), needed, key_hash uint64 [n], part_status
+    uint32 [n_seg, 4]: flags, placed, unplaced, dead); raises RamcrcError (code
+    EINVAL) where the device form refuses."""
+    from . import segments as _seg
+    segments = np.ascontiguousarray(segments, np.uint8)
+    status = np.ascontiguousarray(np.asarray(status).view(np.uint32)).reshape(-1, 4)
+    entries = np.ascontiguousarray(np.asarray(entries).view(np.uint32)).reshape(-1, 4)
+    tablets = np.ascontiguousarray(tablets, _seg.TABLET_DTYPE).reshape(-1)
+    n = entries.shape[0]
+    if segments.size < n_seg * seg_stride or status.shape[0] < n_seg:
+        raise RamcrcError("recovery_partition_host: an array is smaller than its geometry")
+    key_hash = np.zeros(n, np.uint64)
+    pstat = np.zeros((n_seg, 4), np.uint32)
+    p = lambda a: _c.c_void_p(a.ctypes.data) if a.size else None
+    need = _c.c_uint64(0)
+
+    def call(cap):
+        place = np.zeros((cap, 2), np.uint32)
+        rc = lib().ramcrc_recovery_partition_host(p(segments), seg_stride, n_seg, p(status),
+                                                  p(entries), n, p(tablets), tablets.size, n_part,
+                                                  p(place), cap, _c.byref(need), p(key_hash),
+                                                  p(pstat))
+        _check(rc, "ramcrc_recovery_partition_host")
+        return place
+
+    if place_cap is None:
+        call(0)
+        place_cap = need.value
+    place = call(place_cap)
+    return place[:min(need.value, place_cap)], need.value, key_hash, pstat
 
 
 # ---------------------------------------------------------------- device
@@ -446,6 +488,28 @@ class Context:
             out_capacity, _ptr(out_certs), _ptr(out_status), _stream(stream))
         _check(rc, "ramcrc_recovery_append_device")
         return out_certs
+
+    def recovery_partition(self, data, seg_stride, nseg, status, entries, n_entries, tablets,
+                           n_part, place, n_place, part_status, key_hash=None, n_tablets=None,
+                           stream=None):
+        """RecoverySegmentBuilder::build's placement decision for a walk's
+        records (ramcrc_recovery_partition_device): key hash, tablet lookup,
+        liveness.  status, entries, n_entries: a walk's tables; tablets: uint8
+        CUDA holding segments.TABLET_DTYPE records (segments.tablets_tensor);
+        place: int32 CUDA [cap, 2] out and n_place: int64 CUDA [1] out, as
+        recovery_append takes them; part_status: int32 CUDA [nseg, 4] out
+        (flags, placed, unplaced, dead); key_hash: int64 CUDA [entries] out or
+        None.  Asynchronous; a refusal shows in check()."""
+        ecap = 0 if entries is None else entries.shape[0]
+        pcap = 0 if place is None else place.shape[0]
+        if n_tablets is None:
+            n_tablets = 0 if tablets is None else tablets.numel() * tablets.element_size() // 40
+        rc = lib().ramcrc_recovery_partition_device(
+            self._h, _ptr(data), seg_stride, nseg, _ptr(status), _ptr(entries), ecap,
+            _ptr(n_entries), _ptr(tablets), n_tablets, n_part, _ptr(place), pcap, _ptr(n_place),
+            _ptr(key_hash), _ptr(part_status), _stream(stream))
+        _check(rc, "ramcrc_recovery_partition_device")
+        return place
 
     def verify_objects(self, data, seg_stride, entries, n_entries, obj_crc, status, stream=None):
         """Object::computeChecksum + comparison for every object record of a walk."""

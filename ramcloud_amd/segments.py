@@ -33,6 +33,16 @@ SEG_SOURCE_BAD = 128    # ramcrc_append_status.flags: the source segment failed 
 # ramcrc_placement, ramcrc_append_status, and the records and certificates they go with
 PLACEMENT_DTYPE = np.dtype([("record", "<u4"), ("partition", "<u4")])
 APPEND_STATUS_DTYPE = np.dtype([("flags", "<u4"), ("entries", "<u4")])
+SEG_NO_HEADER = 512     # ramcrc_partition_status.flags: a placed record without a SEGHEADER
+SEG_MALFORMED = 1024    # ramcrc_partition_status.flags: a record too short for its fields
+# ramcrc_tablet and ramcrc_partition_status (ramcrc_recovery_partition_device / _host)
+TABLET_DTYPE = np.dtype([("table_id", "<u8"), ("start_key_hash", "<u8"), ("end_key_hash", "<u8"),
+                         ("ctime_segment_id", "<u8"), ("ctime_offset", "<u4"),
+                         ("partition", "<u4")])
+PARTITION_STATUS_DTYPE = np.dtype([("flags", "<u4"), ("placed", "<u4"), ("unplaced", "<u4"),
+                                   ("dead", "<u4")])
+LOG_ENTRY_TYPE_SEGHEADER = 1    # src/LogEntryTypes.h:32
+LOG_ENTRY_TYPE_RPCRESULT = 7    # src/LogEntryTypes.h:50
 LOG_ENTRY_TYPE_OBJ = 2          # src/LogEntryTypes.h:35
 LOG_ENTRY_TYPE_OBJTOMB = 3      # src/LogEntryTypes.h:38
 LOG_ENTRY_TYPE_SAFEVERSION = 5  # src/LogEntryTypes.h:44
@@ -52,6 +62,28 @@ REPLAY_HEADER_BYTES = {LOG_ENTRY_TYPE_OBJ: 24, LOG_ENTRY_TYPE_OBJTOMB: 32,
 REPLAY_SEED = 0x5245504C   # "REPL": value bytes of segment i use seed REPLAY_SEED + i
 OBJECT_OVERHEAD = 24 + 1 + 2 + 8   # Object::Header + KeyCount + CumulativeKeyLength + key
 MIN_REPLAY_ENTRY = 1 + 1 + 12      # EntryHeader + 1 length byte + ObjectSafeVersion::Header
+
+
+def tablets_array(rows):
+    """TABLET_DTYPE array from (table_id, start_key_hash, end_key_hash,
+    ctime_segment_id, ctime_offset, partition) rows."""
+    a = np.zeros(len(rows), TABLET_DTYPE)
+    for i, row in enumerate(rows):
+        a[i] = tuple(int(v) for v in row)
+    return a
+
+
+def tablets_tensor(tablets, device="cuda"):
+    """A tablet list (TABLET_DTYPE array, or rows for tablets_array) as the
+    uint8 device tensor Context.recovery_partition takes."""
+    import torch
+    if not (isinstance(tablets, np.ndarray) and tablets.dtype == TABLET_DTYPE):
+        tablets = tablets_array(tablets)
+    raw = np.ascontiguousarray(tablets).view(np.uint8).reshape(-1)
+    t = torch.zeros(max(raw.size, 40), dtype=torch.uint8, device=device)
+    if raw.size:
+        t[:raw.size] = torch.from_numpy(raw.copy()).to(device)
+    return t[:raw.size] if raw.size else t[:0]
 
 
 def entry_bytes(value_len):
