@@ -211,6 +211,37 @@ class Crc32CBatch {
     }
 
     /**
+     * On a recovery master: the decision ObjectManager::replaySegment makes
+     * after each checksum (src/ObjectManager.cc:671-734, :766-867) for the
+     * objects and tombstones a deviceReplayVerify (or a walk) left in HBM.
+     * Per key the highest version is kept, a tombstone before an object of the
+     * same version.  d_winner (nullable) receives every participant's winner
+     * (a record is live when d_winner[i] == i, RAMCRC_RESOLVE_NONE for records
+     * that take no part), d_live / d_nLive the live records as the {record, 0}
+     * list deviceRecoveryAppend takes with partitions = 1, d_counts the
+     * counters and the recovered safe version.  d_keyHash is
+     * deviceRecoveryPartition's output for the same table, or NULL to have
+     * the hashes computed: see ramcrc_replay_resolve_device.  The call decides
+     * and inserts nothing.  Returns after the kernels finished on `stream`;
+     * throws when the call was refused (a record table that names a replica
+     * >= count).
+     */
+    void
+    deviceReplayResolve(const void* d_base, uint64_t stride, uint64_t count,
+                        const ramcrc_seg_status* d_status, const ramcrc_seg_entry* d_entries,
+                        uint64_t entriesCap, const uint64_t* d_nEntries,
+                        const uint64_t* d_keyHash, uint32_t* d_winner, ramcrc_placement* d_live,
+                        uint64_t liveCap, uint64_t* d_nLive, ramcrc_resolve_counts* d_counts,
+                        void* stream = NULL)
+    {
+        check(ramcrc_replay_resolve_device(context(), d_base, stride, count, d_status, d_entries,
+                                           entriesCap, d_nEntries, d_keyHash, d_winner, d_live,
+                                           liveCap, d_nLive, d_counts, stream),
+              "ramcrc_replay_resolve_device");
+        sync(stream);
+    }
+
+    /**
      * Object::assembleForLog's checksum for a batch of serialized objects
      * (the write path, src/ObjectManager.cc:1274): header.checksum of every
      * object (Object::Header + keysAndValue, src/Object.h:137-182) is set to

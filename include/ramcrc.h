@@ -41,7 +41,8 @@ enum {
     RAMCRC_EREFUSED = -6, /* a launch found more chunks than the context's scratch holds, or
                              ramcrc_recovery_append_device a placement list it refuses, or
                              ramcrc_recovery_partition_device a tablet list or record table
-                             it refuses, and wrote none of its outputs (see ramcrc_ctx_check) */
+                             it refuses, or ramcrc_replay_resolve_device a record table it
+                             refuses, and wrote none of its outputs (see ramcrc_ctx_check) */
     RAMCRC_EINTERNAL = -7, /* a small-entry launch found its bin layout inconsistent with the
                              entries it binned and wrote none of its small-entry outputs.
                              Only a corrupted bin table produces it (the TEST_DIRTY_BINS
@@ -441,6 +442,112 @@ int ramcrc_recovery_partition_host(const void* base, uint64_t seg_stride, uint64
                                    uint32_t n_part, ramcrc_placement* place, uint64_t place_cap,
                                    uint64_t* n_place, uint64_t* key_hash,
                                    ramcrc_partition_status* part_status);
+
+/* The decision ObjectManager::replaySegment makes after each checksum check
+ * (src/ObjectManager.cc:671-734 for objects, :766-867 for tombstones): is this
+ * object or tombstone the newest thing known for its key, or is it discarded?
+ * A recovering partition's table starts empty, so the outcome is a function of
+ * the batch alone, and this call computes it for every walked record at once.
+ * It also writes the survivors as a {record, 0} list that
+ * ramcrc_recovery_append_device takes unchanged with n_part = 1, so walk ->
+ * verify -> resolve -> append compacts recovery segments into side-log-shaped
+ * segments that hold only what the master keeps, without a host round trip.
+ * The call decides; it inserts nothing (the master's hash table and log stay
+ * the master's).
+ *
+ * Inputs are a walk's outputs over n_seg segments (d_status, d_entries,
+ * *d_n_entries; min(*d_n_entries, entries_cap) records are read).
+ *
+ * Participants.  A record takes part when it is an OBJ or OBJTOMB record of a
+ * segment whose status has RAMCRC_SEG_OK and is well-formed by the partition
+ * call's rules above (fields, first key of a multi-key object, malformed
+ * records).  Nothing else takes part: other types -- PREP included, whose
+ * replay depends on the order of arrival (:966-989) --, records of segments
+ * without RAMCRC_SEG_OK, and malformed OBJ / OBJTOMB records of OK segments,
+ * which are counted in `malformed`.  A failed object checksum does not exclude
+ * a record: the reference only logs it (:664-669).
+ *
+ * Key identity.  Two participants have the same key when they share the table
+ * id (all 64 bits: OBJ u64 at payload 16, OBJTOMB u64 at 0), the key length,
+ * and the key bytes (OBJ: the first key, as the partition call finds it;
+ * OBJTOMB: [32, length)).  The empty key is a key.  The 64-bit key hash only
+ * narrows the search; equal hashes never make two keys equal.
+ *
+ * Version.  OBJ: u64 at payload 8 (Object::Header::version, src/Object.h:171);
+ * OBJTOMB: u64 at 16 (objectVersion, :324).  Compared unsigned, all 64 bits.
+ *
+ * Winner of a key, in order: the highest version; among those a tombstone
+ * before an object (:693 discards an object at <=, :786 a tombstone only at
+ * <); among those the lowest record index.  This is the content of the
+ * reference's hash table after replaying the table's records in table order.
+ * For any other order it is the same, except for which of several records of
+ * identical version and type is kept.  The tie rule among equal tombstones is
+ * this library's own: the reference asserts that the case does not occur
+ * (:790-793).
+ *
+ * safe_version is the maximum, over the SAFEVERSION records of at least 12
+ * bytes in OK segments (readable: no RAMCRC_SEG_ENTRY_OVERLONG, payload inside
+ * seg_stride), of the u64 at payload 0 (:875, :901), or 0 when there is none.
+ *
+ * What the call does not do: PREP and the other transaction records
+ * (RPCRESULT, PREPTOMB, TXDECISION, TXPLIST), which take no part; the
+ * raiseSafeVersion(version + 1) of a kept tombstone at :797, which depends on
+ * the replay order and is not folded into safe_version; the tombstones
+ * sequential replay synthesizes for an object it overwrites (:697-717,
+ * :804-835); and insertion into the master's table.  A surviving tombstone is
+ * listed as it lies in its segment: the reference rewrites its segment id,
+ * timestamp and checksum before it logs it (:845-851), which remains the
+ * caller's job. */
+#define RAMCRC_RESOLVE_NONE 0xFFFFFFFFu
+typedef struct ramcrc_resolve_counts {
+    uint64_t objects, tombstones;            /* participants */
+    uint64_t live_objects, live_tombstones;  /* winners (one per distinct key) */
+    uint64_t malformed;                      /* malformed OBJ / OBJTOMB records of OK segments */
+    uint64_t safe_version;
+} ramcrc_resolve_counts;
+
+/* d_key_hash (nullable, one per record read) is the partition call's
+ * d_key_hash output for the same table; with NULL the call computes
+ * Key::getHash itself.  A caller's hashes must be a function of (table id,
+ * key): equal keys with different hashes are treated as different keys.
+ *
+ * d_winner (nullable, one slot per record read) receives for every
+ * participant the record index of the winner of its key, and
+ * RAMCRC_RESOLVE_NONE for every other record; record i is live exactly when
+ * d_winner[i] == i.  d_live receives {record, 0} for every live record,
+ * objects and tombstones alike, in increasing record order, and *d_n_live
+ * (device) the needed count; past live_cap only the first live_cap entries are
+ * written, slots at or past the list's end are never written, and this call
+ * does not refuse: the append then does, by its own *d_n_place > place_cap
+ * rule.  d_counts (device) receives the counters.
+ *
+ * The call refuses -- *d_n_live = 0 and zeroed *d_counts are its only outputs,
+ * and ramcrc_ctx_check returns RAMCRC_EREFUSED -- when a record names a
+ * segment >= n_seg.
+ *
+ * d_base 16-byte aligned, seg_stride a multiple of 16 (the walk's rules);
+ * n_seg, entries_cap, live_cap < 2^32 - 1.  Records are grouped in an
+ * open-addressed table of S(n) slots, S(n) the smallest power of two that is
+ * at least 64 and at least 2 * n, sized on the device from the walked count.
+ * Scratch comes from the context: after ramcrc_ctx_reserve(ctx, 16 + 6 *
+ * S(entries_cap), 2 * entries_cap), or after one call of the same shape, it
+ * does not allocate.  Stream-ordered, asynchronous. */
+int ramcrc_replay_resolve_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                 const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                 const uint64_t* d_n_entries, const uint64_t* d_key_hash,
+                                 uint32_t* d_winner, ramcrc_placement* d_live, uint64_t live_cap,
+                                 uint64_t* d_n_live, ramcrc_resolve_counts* d_counts, void* stream);
+
+/* The same on the host, single-threaded: host pointers, n_entries records,
+ * *n_live receives the needed count (at most live_cap entries are written).
+ * Returns RAMCRC_EINVAL where the device form refuses (nothing is written).
+ * No alignment rules. */
+int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                               const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                               uint64_t n_entries, const uint64_t* key_hash, uint32_t* winner,
+                               ramcrc_placement* live, uint64_t live_cap, uint64_t* n_live,
+                               ramcrc_resolve_counts* counts);
 
 /* ObjectManager::replaySegment's checksum checks for every record of a walk
  * whose segment passed the metadata check (d_status flags RAMCRC_SEG_OK;

@@ -41,6 +41,8 @@
 //    segments, and the records the replay checks read.
 //  * k_app_* -- walked records appended into per-partition recovery segments,
 //    with their certificates.
+//  * k_res_* -- which replayed objects and tombstones a recovery master keeps
+//    (DESIGN.md 5.10).
 //
 // The kernels live in per-family parts included below, in this order, into
 // this one translation unit (shared __device__ tables and LDS layouts, no
@@ -55,6 +57,7 @@
 //   dev_checks.inc   k_obj_compare, k_obj_stamp, certificate kernels
 //   dev_append.inc   k_app_mark, k_app_scan, k_app_copy (recovery-segment append)
 //   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
+//   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -72,6 +75,7 @@
 #include "walk_rules.h"
 #include "murmur3.h"
 #include "partition_rules.h"
+#include "resolve_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -92,6 +96,7 @@ using ramcrc::OpTable;
 #include "dev_checks.inc"
 #include "dev_append.inc"
 #include "dev_partition.inc"
+#include "dev_resolve.inc"
 
 extern "C" {
 
@@ -1091,6 +1096,79 @@ int ramcrc_recovery_partition_device(ramcrc_ctx* c, const void* d_base, uint64_t
     hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(kPartThreads), 0, s, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_part_emit, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_resolve_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                 const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                 const uint64_t* d_n_entries, const uint64_t* d_key_hash,
+                                 uint32_t* d_winner, ramcrc_placement* d_live, uint64_t live_cap,
+                                 uint64_t* d_n_live, ramcrc_resolve_counts* d_counts, void* stream)
+{
+    if (!c || n_seg >= 0xFFFFFFFFull || entries_cap >= 0xFFFFFFFFull || live_cap >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (!d_n_live || !d_counts || !d_n_entries || (n_seg && (!d_base || !d_status)) ||
+        (entries_cap && !d_entries) || (live_cap && !d_live))
+        return RAMCRC_EINVAL;
+    const uint64_t B = reinterpret_cast<uint64_t>(d_base);
+    if ((B & 15) || (seg_stride & 15) || (seg_stride && n_seg > UINT64_MAX / seg_stride))
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch words in the chunk-partial buffer: the head (refusal word and
+    // counters), then six words per slot of the largest grouping table this
+    // shape can need; a version and a slot per record in the plan buffer and
+    // the tile sums in the group prefixes (ramcrc.h states these sizes)
+    const uint64_t slots = ramcrc_res::slots_for(entries_cap);
+    int rc = reserve_locked(c, kResHeadWords + 2 * kResSlotWords * slots, 2 * entries_cap);
+    if (rc)
+        return rc;
+    ResDesc a{};
+    a.base = B;
+    a.stride = seg_stride;
+    a.nseg = n_seg;
+    a.status = d_status;
+    a.entries = reinterpret_cast<const u32x4*>(d_entries);
+    a.ecap = entries_cap;
+    a.n_entries = d_n_entries;
+    a.key_hash = d_key_hash;
+    a.winner = d_winner;
+    a.live = reinterpret_cast<uint2*>(d_live);
+    a.lcap = live_cap;
+    a.n_live = d_n_live;
+    a.counts_out = d_counts;
+    a.refuse = c->partials;
+    a.counts = reinterpret_cast<unsigned long long*>(c->partials + 4);
+    a.slots = reinterpret_cast<unsigned long long*>(c->partials + kResHeadWords);
+    a.rec_ver = c->plan_local;
+    a.rec_slot = c->plan_local + entries_cap;
+    a.tile_sum = c->group_pref;
+    a.ctx_status = c->status;
+    HIPCHK(hipMemsetAsync(c->partials, 0, kResHeadWords * sizeof(uint32_t), s));
+    const uint64_t cap_grid = uint64_t(8) * c->ncu;
+    auto grid_of = [&](uint64_t items, uint64_t per) {
+        uint64_t gr = (items + per - 1) / per;
+        return dim3(uint32_t(gr < 1 ? 1 : (gr > cap_grid ? cap_grid : gr)));
+    };
+    hipLaunchKernelGGL(k_res_zero, grid_of(kResSlotWords * slots, kPartThreads), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (d_key_hash)
+        hipLaunchKernelGGL(k_res_insert<true>, grid_of(entries_cap, kPartThreads), dim3(kPartThreads),
+                           0, s, a);
+    else
+        hipLaunchKernelGGL(k_res_insert<false>, grid_of(entries_cap, kPartThreads), dim3(kPartThreads),
+                           0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_res_pick, grid_of(entries_cap, kPartThreads), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_res_tiles, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_res_scan, dim3(1), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_res_emit, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }

@@ -21,6 +21,7 @@
 #include "gf2.h"
 #include "murmur3.h"
 #include "partition_rules.h"
+#include "resolve_rules.h"
 
 namespace {
 
@@ -449,6 +450,122 @@ int ramcrc_recovery_partition_host(const void* base, uint64_t seg_stride, uint64
                                          0u, 0u};
     }
     *n_place = np;
+    return RAMCRC_OK;
+}
+
+// ObjectManager::replaySegment's newest-wins decision on the host: one pass
+// over the table in record order into an open-addressed table of the keys
+// (the rules of resolve_rules.h), then the verdicts.
+int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                               const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                               uint64_t n_entries, const uint64_t* key_hash, uint32_t* winner,
+                               ramcrc_placement* live, uint64_t live_cap, uint64_t* n_live,
+                               ramcrc_resolve_counts* counts)
+{
+    namespace rp = ramcrc_part;
+    namespace rr = ramcrc_res;
+    if (n_seg >= 0xFFFFFFFFull || n_entries >= 0xFFFFFFFFull || live_cap >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (!n_live || !counts || (n_seg && (!base || !status)) || (n_entries && !entries) ||
+        (live_cap && !live))
+        return RAMCRC_EINVAL;
+    if (seg_stride && n_seg > UINT64_MAX / seg_stride)
+        return RAMCRC_EINVAL;
+    for (uint64_t i = 0; i < n_entries; i++)
+        if (entries[i].segment >= n_seg)
+            return RAMCRC_EINVAL;
+    struct Rd {
+        const uint8_t* pay;
+        uint32_t u8(uint32_t o) const { return pay[o]; }
+        uint32_t u16(uint32_t o) const { return ld16(pay + o); }
+        uint32_t u32(uint32_t o) const { return ld32(pay + o); }
+        uint64_t u64(uint32_t o) const { return ld64(pay + o); }
+    };
+    struct Rec {   // a participant
+        uint64_t table_id, version, hash;
+        const uint8_t* key;
+        uint32_t key_len;
+        uint64_t slot;   // ~0: no participant
+    };
+    struct Slot {
+        uint32_t first;   // 1 + the record that claimed the slot (its key is the slot's), 0: empty
+        uint32_t best;    // the key's winner so far
+    };
+    const uint64_t nslots = rr::slots_for(n_entries), mask = nslots - 1;
+    Rec* const recs = static_cast<Rec*>(calloc(n_entries ? n_entries : 1, sizeof(Rec)));
+    Slot* const slots = static_cast<Slot*>(calloc(nslots, sizeof(Slot)));
+    if (!recs || !slots) {
+        free(recs);
+        free(slots);
+        return RAMCRC_ENOMEM;
+    }
+    const uint8_t* const b = static_cast<const uint8_t*>(base);
+    ramcrc_resolve_counts ct{0, 0, 0, 0, 0, 0};
+    for (uint64_t i = 0; i < n_entries; i++) {
+        const ramcrc_seg_entry& r = entries[i];
+        const uint32_t type = r.header & 0x3f;
+        recs[i].slot = ~0ull;
+        if (!(status[r.segment].flags & RAMCRC_SEG_OK))
+            continue;
+        const uint64_t pay = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+        const bool readable = !(r.header & RAMCRC_SEG_ENTRY_OVERLONG) && pay + r.length <= seg_stride;
+        const Rd rd{b + r.segment * seg_stride + pay};
+        if (type == RAMCRC_LOG_ENTRY_TYPE_SAFEVERSION) {
+            if (readable && r.length >= rr::kSafeVersionBytes && rd.u64(0) > ct.safe_version)
+                ct.safe_version = rd.u64(0);
+            continue;
+        }
+        if (!rr::resolved_type(type))
+            continue;
+        const rp::Parsed p = rp::parse(type, r.length, readable, rd);
+        if (p.kind == rp::kMalformed) {
+            ct.malformed++;
+            continue;
+        }
+        (type == RAMCRC_LOG_ENTRY_TYPE_OBJ ? ct.objects : ct.tombstones)++;
+        Rec& me = recs[i];
+        me.table_id = p.table_id;
+        me.key = rd.pay + p.key_off;
+        me.key_len = p.key_len;
+        me.version = rr::version(type, rd);
+        me.hash = key_hash ? key_hash[i] : ramcrc::key_hash(me.table_id, me.key, me.key_len);
+        for (uint64_t s = me.hash & mask;; s = (s + 1) & mask) {   // load <= 0.5: the chain ends
+            Slot& sl = slots[s];
+            if (!sl.first) {
+                sl.first = uint32_t(i) + 1;
+                sl.best = uint32_t(i);
+                me.slot = s;
+                break;
+            }
+            const Rec& k = recs[sl.first - 1];
+            if (k.hash != me.hash || k.table_id != me.table_id || k.key_len != me.key_len ||
+                (me.key_len && memcmp(k.key, me.key, me.key_len)))
+                continue;
+            const Rec& w = recs[sl.best];
+            if (rr::beats(me.version, rr::rank(type, i), w.version,
+                          rr::rank(entries[sl.best].header & 0x3f, sl.best)))
+                sl.best = uint32_t(i);
+            me.slot = s;
+            break;
+        }
+    }
+    uint64_t nl = 0;
+    for (uint64_t i = 0; i < n_entries; i++) {
+        const uint32_t w = recs[i].slot == ~0ull ? RAMCRC_RESOLVE_NONE : slots[recs[i].slot].best;
+        if (winner)
+            winner[i] = w;
+        if (w != i)
+            continue;
+        ((entries[i].header & 0x3f) == RAMCRC_LOG_ENTRY_TYPE_OBJ ? ct.live_objects
+                                                                  : ct.live_tombstones)++;
+        if (nl < live_cap)
+            live[nl] = ramcrc_placement{uint32_t(i), 0u};
+        nl++;
+    }
+    free(recs);
+    free(slots);
+    *n_live = nl;
+    *counts = ct;
     return RAMCRC_OK;
 }
 

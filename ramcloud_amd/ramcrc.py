@@ -96,6 +96,10 @@ def lib():
                                                    vp, u64, vp, vp, vp, vp]),
         "ramcrc_recovery_partition_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u32, u32, vp, u64,
                                                  _c.POINTER(u64), vp, vp]),
+        "ramcrc_replay_resolve_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64,
+                                               vp, vp, vp]),
+        "ramcrc_replay_resolve_host": (i32, [vp, u64, u64, vp, vp, u64, vp, vp, vp, u64,
+                                             _c.POINTER(u64), vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -298,6 +302,39 @@ def recovery_partition_host(segments, seg_stride, n_seg, status, entries, tablet
         place_cap = need.value
     place = call(place_cap)
     return place[:min(need.value, place_cap)], need.value, key_hash, pstat
+
+
+def replay_resolve_host(segments, seg_stride, n_seg, status, entries, key_hash=None,
+                        live_cap=None):
+    """ObjectManager::replaySegment's newest-wins decision on the host
+    (ramcrc_replay_resolve_host).  segments uint8; status uint32 [n_seg, 4];
+    entries uint32 [n, 4]; key_hash uint64 [n] or None (computed).  live_cap:
+    the list's capacity (None: one slot per record).  Returns (winner uint32
+    [n], live uint32 [m, 2] with m = min(needed, live_cap), needed, counts: a
+    segments.RESOLVE_COUNTS_DTYPE scalar); raises RamcrcError (code EINVAL)
+    where the device form refuses."""
+    from . import segments as _seg
+    segments = np.ascontiguousarray(segments, np.uint8)
+    status = np.ascontiguousarray(np.asarray(status).view(np.uint32)).reshape(-1, 4)
+    entries = np.ascontiguousarray(np.asarray(entries).view(np.uint32)).reshape(-1, 4)
+    n = entries.shape[0]
+    if segments.size < n_seg * seg_stride or status.shape[0] < n_seg:
+        raise RamcrcError("replay_resolve_host: an array is smaller than its geometry")
+    if key_hash is not None:
+        key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+        if key_hash.size < n:
+            raise RamcrcError("replay_resolve_host: fewer hashes than records")
+    cap = n if live_cap is None else int(live_cap)
+    winner = np.zeros(n, np.uint32)
+    live = np.zeros((cap, 2), np.uint32)
+    counts = np.zeros(1, _seg.RESOLVE_COUNTS_DTYPE)
+    need = _c.c_uint64(0)
+    p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    rc = lib().ramcrc_replay_resolve_host(p(segments), seg_stride, n_seg, p(status), p(entries), n,
+                                          p(key_hash), p(winner), p(live), cap, _c.byref(need),
+                                          p(counts))
+    _check(rc, "ramcrc_replay_resolve_host")
+    return winner, live[:min(need.value, cap)], need.value, counts[0]
 
 
 # ---------------------------------------------------------------- device
@@ -510,6 +547,26 @@ class Context:
             _ptr(key_hash), _ptr(part_status), _stream(stream))
         _check(rc, "ramcrc_recovery_partition_device")
         return place
+
+    def replay_resolve(self, data, seg_stride, nseg, status, entries, n_entries, live, n_live,
+                       counts, key_hash=None, winner=None, stream=None):
+        """Which replayed objects and tombstones a recovery master keeps
+        (ramcrc_replay_resolve_device): per key the highest version, a
+        tombstone before an object of the same version.  status, entries,
+        n_entries: a walk's tables; key_hash: int64 CUDA [entries] (the
+        partition call's output) or None (computed); winner: int32 CUDA
+        [entries] out or None; live: int32 CUDA [cap, 2] out and n_live: int64
+        CUDA [1] out, as recovery_append takes them with n_part = 1; counts:
+        int64 CUDA [6] out (segments.RESOLVE_COUNTS_DTYPE).  Asynchronous; a
+        refusal shows in check()."""
+        ecap = 0 if entries is None else entries.shape[0]
+        lcap = 0 if live is None else live.shape[0]
+        rc = lib().ramcrc_replay_resolve_device(
+            self._h, _ptr(data), seg_stride, nseg, _ptr(status), _ptr(entries), ecap,
+            _ptr(n_entries), _ptr(key_hash), _ptr(winner), _ptr(live), lcap, _ptr(n_live),
+            _ptr(counts), _stream(stream))
+        _check(rc, "ramcrc_replay_resolve_device")
+        return live
 
     def verify_objects(self, data, seg_stride, entries, n_entries, obj_crc, status, stream=None):
         """Object::computeChecksum + comparison for every object record of a walk."""

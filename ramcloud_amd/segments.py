@@ -41,6 +41,11 @@ TABLET_DTYPE = np.dtype([("table_id", "<u8"), ("start_key_hash", "<u8"), ("end_k
                          ("partition", "<u4")])
 PARTITION_STATUS_DTYPE = np.dtype([("flags", "<u4"), ("placed", "<u4"), ("unplaced", "<u4"),
                                    ("dead", "<u4")])
+# ramcrc_resolve_counts and the no-winner mark (ramcrc_replay_resolve_device / _host)
+RESOLVE_COUNTS_DTYPE = np.dtype([("objects", "<u8"), ("tombstones", "<u8"), ("live_objects", "<u8"),
+                                 ("live_tombstones", "<u8"), ("malformed", "<u8"),
+                                 ("safe_version", "<u8")])
+RESOLVE_NONE = 0xFFFFFFFF
 LOG_ENTRY_TYPE_SEGHEADER = 1    # src/LogEntryTypes.h:32
 LOG_ENTRY_TYPE_RPCRESULT = 7    # src/LogEntryTypes.h:50
 LOG_ENTRY_TYPE_OBJ = 2          # src/LogEntryTypes.h:35
