@@ -281,8 +281,93 @@ class Crc32CBatch {
     int device;
     ramcrc_ctx* ctx;
 
+    friend class ReplayTable;
+
     Crc32CBatch(const Crc32CBatch&);             // not copyable
     Crc32CBatch& operator=(const Crc32CBatch&);
+};
+
+/**
+ * deviceReplayResolve's decision fed batch by batch: a table on the GPU that
+ * outlives a call (ramcrc_replay_table_*, the rules are in include/ramcrc.h).
+ * MasterService::recover (src/MasterService.cc:3501-3720) calls add() for
+ * every recovery segment, or group of them, as it arrives and has been
+ * verified, and at the end live() and Crc32CBatch::deviceRecoveryAppend with
+ * one partition for every batch.  Every array given to add() stays allocated
+ * and unchanged until reset() or the table's destruction.  The table belongs
+ * to `batch`'s context and must be destroyed before it.  add(), live() and
+ * stats() are asynchronous on `stream`; Crc32CBatch::sync(stream) waits and
+ * throws if the table was spoiled.  Errors throw like Crc32CBatch's.
+ */
+class ReplayTable {
+  public:
+    ReplayTable(Crc32CBatch& batch, uint64_t keyCap, uint32_t maxBatches)
+        : table(NULL)
+    {
+        check(ramcrc_replay_table_create(batch.context(), keyCap, maxBatches, &table),
+              "ramcrc_replay_table_create");
+    }
+
+    ~ReplayTable()
+    {
+        if (table)
+            ramcrc_replay_table_destroy(table);
+    }
+
+    /// Empties the table and forgets its batches; stream-ordered.
+    void
+    reset(void* stream = NULL)
+    {
+        check(ramcrc_replay_table_reset(table, stream), "ramcrc_replay_table_reset");
+    }
+
+    /// Resolves one walk's records into the table; d_work: entriesCap 64-bit
+    /// words of the caller's, which live() reads.  Returns the batch number.
+    uint32_t
+    add(const void* d_base, uint64_t stride, uint64_t count, const ramcrc_seg_status* d_status,
+        const ramcrc_seg_entry* d_entries, uint64_t entriesCap, const uint64_t* d_nEntries,
+        const uint64_t* d_keyHash, uint64_t* d_work, void* stream = NULL)
+    {
+        uint32_t batch = 0;
+        check(ramcrc_replay_table_add_device(table, d_base, stride, count, d_status, d_entries,
+                                             entriesCap, d_nEntries, d_keyHash, d_work, &batch,
+                                             stream),
+              "ramcrc_replay_table_add_device");
+        return batch;
+    }
+
+    /// The verdict on one batch as the table stands now: d_winner (nullable),
+    /// the {record, 0} list deviceRecoveryAppend takes with one partition over
+    /// that batch's segments, and the counters.
+    void
+    live(uint32_t batch, ramcrc_replay_ref* d_winner, ramcrc_placement* d_live, uint64_t liveCap,
+         uint64_t* d_nLive, ramcrc_resolve_counts* d_counts, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_live_device(table, batch, d_winner, d_live, liveCap, d_nLive,
+                                              d_counts, stream),
+              "ramcrc_replay_table_live_device");
+    }
+
+    /// Keys, winners, safe version and batches of the whole table.
+    void
+    stats(ramcrc_replay_table_stats* d_stats, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_stats_device(table, d_stats, stream),
+              "ramcrc_replay_table_stats_device");
+    }
+
+  private:
+    static void
+    check(int rc, const char* what)
+    {
+        if (rc != RAMCRC_OK)
+            RAMCRC_BATCH_THROW(std::string(what) + ": " + ramcrc_strerror(rc));
+    }
+
+    ramcrc_replay_table* table;
+
+    ReplayTable(const ReplayTable&);             // not copyable
+    ReplayTable& operator=(const ReplayTable&);
 };
 
 /**

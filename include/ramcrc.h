@@ -549,6 +549,141 @@ int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n
                                ramcrc_placement* live, uint64_t live_cap, uint64_t* n_live,
                                ramcrc_resolve_counts* counts);
 
+/* The same decision fed batch by batch: a table that outlives a call.
+ * MasterService::recover (src/MasterService.cc:3501-3720) replays recovery
+ * segments as they arrive from the backups (:3632), so every lookup after the
+ * first segment meets a table that is not empty (src/ObjectManager.cc:678-696,
+ * :766-793).  A replay table takes one walk's records per add and gives, at
+ * any time, the verdict on any added batch as the table stands: exactly
+ * ramcrc_replay_resolve_device's over everything added so far.
+ *
+ * Reused rules.  Participants, key identity, version, safe_version and the
+ * malformed count are ramcrc_replay_resolve_device's above (resolve_rules.h,
+ * partition_rules.h).
+ *
+ * Record identity.  A record is named {batch, record}.  Batches are numbered
+ * 0, 1, 2 ... in the order they are added; "none" is {0xFFFFFFFF, 0xFFFFFFFF}.
+ *
+ * Winner of a key, over all batches added so far, in order: the highest
+ * version; then a tombstone before an object; then the lowest {batch,
+ * record}, batch first.
+ *
+ * The defining property.  Let C be the concatenation of the added batches'
+ * record tables in add order, with segment numbers offset by the earlier
+ * batches' n_seg.  The winners are what ramcrc_replay_resolve_host returns
+ * for C, with global index i mapped back to {batch, record}.  The order in
+ * which batches are added changes only which of several records of identical
+ * version and type is kept.
+ *
+ * Hashes.  d_key_hash, where given, must be a function of (table id, key),
+ * the same function for every add into a table until it is reset; NULL means
+ * Key::getHash, computed in the call.  Under that rule two participants are
+ * the same key exactly when table id, key length and key bytes are equal, and
+ * that is what the table compares: it does not reject by hash.
+ *
+ * Lifetime.  A batch's segment bytes, status array, record table, hashes and
+ * work array stay allocated and unchanged until the table is reset or
+ * destroyed: a later add reads an earlier claimant's key from its segment, as
+ * the one-call does within a batch, and a live query reads the work array.
+ *
+ * Spoiling.  Two things spoil a table: a record that names a segment >= n_seg,
+ * and an add after which the table holds more than key_cap keys or in which a
+ * record found no slot.  The refusal word is then set and ramcrc_ctx_check
+ * returns RAMCRC_EREFUSED.  Until the next reset every add is a no-op on the
+ * device, and every live and stats call writes only *d_n_live = 0 and zeroed
+ * structures (spoiled = 1); d_winner and d_live stay untouched.  The add that
+ * spoils has changed the table before it finds out: a pre-pass that validated
+ * a batch before touching the table would cost one more read of the record
+ * table per add, and is not made.
+ *
+ * Not done, as in the one-call: the synthesized tombstone for an overwritten
+ * object (:697-717, :804-835), raiseSafeVersion(version + 1) (:797), the
+ * rewrite of a kept tombstone's header, PREP and the other transaction
+ * records, and insertion into the master's own table.
+ *
+ * Concurrency.  All calls are stream-ordered and asynchronous; calls on one
+ * table are serialised by the handle; a caller who uses several streams
+ * orders them. */
+typedef struct { uint32_t batch, record; } ramcrc_replay_ref;
+typedef struct ramcrc_replay_table ramcrc_replay_table;
+typedef struct ramcrc_replay_table_stats {
+    uint64_t keys;                           /* claimed slots: distinct keys */
+    uint64_t live_objects, live_tombstones;  /* winners over the whole table */
+    uint64_t safe_version;
+    uint64_t batches;                        /* added since the last reset */
+    uint64_t spoiled;                        /* 1: every other field is 0 */
+} ramcrc_replay_table_stats;
+#define RAMCRC_REPLAY_TABLE_MAX_BATCHES 65536u
+
+/* One device allocation is made here and none afterwards: 16 + 32 *
+ * max_batches + 4 * S 64-bit words, S = S(key_cap) slots of four words (the
+ * key's highest version, its pick, its claim, one spare, so that a slot never
+ * straddles a 128-byte line), a descriptor and a line of counters per batch,
+ * a head of counters with the refusal word.  1 <= max_batches <= 65,536, so
+ * that a rank (is_object << 48 | batch << 32 | record) fits one word; key_cap
+ * < 2^32 - 1.  The table belongs to ctx and must be destroyed before it. */
+int ramcrc_replay_table_create(ramcrc_ctx* ctx, uint64_t key_cap, uint32_t max_batches,
+                               ramcrc_replay_table** out);
+int ramcrc_replay_table_destroy(ramcrc_replay_table* t);
+
+/* Empties the table and forgets its batches (their arrays are the caller's
+ * again once the stream reaches this point).  Stream-ordered, on the device. */
+int ramcrc_replay_table_reset(ramcrc_replay_table* t, void* stream);
+
+/* Resolves one walk's records (d_status, d_entries, *d_n_entries over n_seg
+ * segments) into the table.  d_work: the caller's array of entries_cap 64-bit
+ * words, opaque; the add writes it and the live query reads it.  *batch (host,
+ * nullable) receives the batch's number, assigned on the host under the
+ * handle's lock.  Pointer, alignment and range rules are the one-call's.  With
+ * max_batches batches already added it returns RAMCRC_EINVAL and launches
+ * nothing. */
+int ramcrc_replay_table_add_device(ramcrc_replay_table* t, const void* d_base, uint64_t seg_stride,
+                                   uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                   const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                   const uint64_t* d_n_entries, const uint64_t* d_key_hash,
+                                   uint64_t* d_work, uint32_t* batch, void* stream);
+
+/* The verdict on one added batch's records as the table stands now; it may be
+ * asked at any time and again after later adds.  d_winner[i] (nullable, one
+ * per record read) is the winner of record i's key, or none.  d_live and
+ * *d_n_live list the batch's records that are winners now, as {record, 0} in
+ * increasing record order: ramcrc_recovery_append_device takes that list
+ * unchanged with n_part = 1, over that batch's segments.  Past live_cap the
+ * one-call's rule holds.  d_counts: objects, tombstones and malformed are the
+ * batch's participants, noted at add time; live_* are the batch's winners
+ * now; safe_version is the table's so far.  RAMCRC_EINVAL for a batch that
+ * has not been added.  The tile sums come from the context's scratch: after
+ * ramcrc_ctx_reserve(ctx, 0, entries_cap) the call does not allocate. */
+int ramcrc_replay_table_live_device(ramcrc_replay_table* t, uint32_t batch,
+                                    ramcrc_replay_ref* d_winner, ramcrc_placement* d_live,
+                                    uint64_t live_cap, uint64_t* d_n_live,
+                                    ramcrc_resolve_counts* d_counts, void* stream);
+
+/* The whole table: one pass over the slots into *d_stats (device). */
+int ramcrc_replay_table_stats_device(ramcrc_replay_table* t, ramcrc_replay_table_stats* d_stats,
+                                     void* stream);
+
+/* The same on the host, single-threaded: host pointers, n_entries records, no
+ * alignment rules, the same lifetime rule.  ramcrc_replay_table_add_host
+ * returns RAMCRC_EINVAL where the device form spoils, and the table is then
+ * spoiled the same way: until the reset every add returns RAMCRC_EINVAL and
+ * does nothing, and live and stats write *n_live = 0 and zeroed structures
+ * (spoiled = 1) and return RAMCRC_OK. */
+typedef struct ramcrc_replay_table_host ramcrc_replay_table_host;
+int ramcrc_replay_table_create_host(uint64_t key_cap, uint32_t max_batches,
+                                    ramcrc_replay_table_host** out);
+int ramcrc_replay_table_destroy_host(ramcrc_replay_table_host* t);
+int ramcrc_replay_table_reset_host(ramcrc_replay_table_host* t);
+int ramcrc_replay_table_add_host(ramcrc_replay_table_host* t, const void* base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* status,
+                                 const ramcrc_seg_entry* entries, uint64_t n_entries,
+                                 const uint64_t* key_hash, uint64_t* work, uint32_t* batch);
+int ramcrc_replay_table_live_host(ramcrc_replay_table_host* t, uint32_t batch,
+                                  ramcrc_replay_ref* winner, ramcrc_placement* live,
+                                  uint64_t live_cap, uint64_t* n_live,
+                                  ramcrc_resolve_counts* counts);
+int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_table_stats* stats);
+
 /* ObjectManager::replaySegment's checksum checks for every record of a walk
  * whose segment passed the metadata check (d_status flags RAMCRC_SEG_OK;
  * records of failed segments are skipped, as RecoverySegmentBuilder::build

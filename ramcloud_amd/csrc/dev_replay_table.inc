@@ -1,0 +1,465 @@
+// The persistent replay table (ramcrc_replay_table_*): k_rtab_zero,
+// k_rtab_open, k_rtab_insert, k_rtab_pick (an add), k_rtab_tiles, k_rtab_scan,
+// k_rtab_emit (a live query), k_rtab_stats (DESIGN.md 5.11).
+// Part of ramcrc_device.hip (one translation unit: the kernels share the
+// g_tab tables, LDS layouts and templates without relocatable device code).
+// Included only from there, after dev_resolve.inc; not a standalone header.
+//
+// ramcrc_replay_resolve_device's decision, fed batch by batch: the grouping
+// table outlives the call, and a key's winner is the winner over every batch
+// added so far.  A record is named {batch, record}; a slot is four 64-bit
+// words, so that it never straddles a 128-byte line:
+//   [0] the key's highest version;
+//   [1] ~(lowest rank at that version), the pick; 0: none;
+//   [2] the claim, batch << 32 | record + 1 of the record whose key is the
+//       slot's; 0: empty;
+//   [3] spare.
+// An add is three launches, none of which waits for another workgroup:
+//   k_rtab_open    one thread writes the batch's descriptor (where its
+//                  segments, tables and work array lie), so that later adds
+//                  can read this batch's keys;
+//   k_rtab_insert  one thread per record: k_res_insert's probe with a 64-bit
+//                  claim, the claimant's key read through its batch's
+//                  descriptor; folds the version into the slot's maximum,
+//                  drops the slot's pick when that raised the maximum, and
+//                  leaves the record's slot in d_work;
+//   k_rtab_pick    the maxima are final: participants at their slot's maximum
+//                  fold ~rank into the pick by maximum.
+// The stale pick is the one hazard a table that stays adds.  Key K wins batch
+// 0 with a tombstone of version 5; batch 1 brings an object of version 7.  The
+// pick still holds the tombstone's ~rank, which is larger than the
+// newcomer's, so a bare maximum would never replace it.  Between adds a pick
+// is always one made at the slot's maximum version, and no launch but
+// k_rtab_pick folds picks; so a lane of the insert whose version strictly
+// raises the maximum (the fetch-max returns what it replaced) knows that the
+// pick in the slot, if any, is of a lower version, and stores 0 (none) to it.
+// Every such lane stores the same value, and the folds begin behind the
+// kernel boundary.  A fresh slot's pick is 0 already, so version 0 needs no
+// rule of its own.
+// A live query reads one batch's d_work and the slots' picks as they stand:
+// k_rtab_tiles (winners, live counts per tile of 1,024 records), k_rtab_scan
+// (one workgroup: offsets, *d_n_live, the counters), k_rtab_emit (the list).
+// Inside insert and pick every access to a slot word is a relaxed
+// agent-scope atomic, loads included; words written by earlier launches lie
+// behind kernel boundaries and are read plainly.  A slot's only key material
+// is its claim, published by the claiming CAS itself, so no lane ever waits
+// for another lane's store, in this batch or an earlier one.
+
+namespace {
+
+constexpr uint64_t kRtabSlotWords = 4;
+constexpr uint64_t kRtabHeadWords = 16;   // 64-bit words before the descriptors
+
+// The head of the table's allocation.
+enum : uint32_t {
+    kRtabRefuse = 0,   // nonzero: spoiled until the next reset
+    kRtabKeys = 1,     // claimed slots
+    kRtabSafe = 2,     // the highest SAFEVERSION seen
+};
+
+// One added batch: 16 words, written by k_rtab_open and only read afterwards
+// (by every later add, for its claimants' keys).
+struct RtabBatch {
+    uint64_t base;              // source segments
+    uint64_t stride;
+    uint64_t nseg;
+    const ramcrc_seg_status* status;
+    const u32x4* entries;       // {segment, offset, length, header}
+    const uint64_t* n_entries;
+    uint64_t ecap;
+    const uint64_t* key_hash;   // nullable: the caller's hashes
+    uint64_t* work;             // [ecap] a participant's slot, kResNone: no participant
+    uint64_t pad[7];
+};
+static_assert(sizeof(RtabBatch) == 128, "a descriptor is one 128-byte line");
+
+// A batch's participants, counted by the insert with atomics: on a line of
+// their own, away from the descriptor the probing lanes read.
+struct RtabCount {
+    unsigned long long objects, tombstones, malformed;
+    uint64_t pad[13];
+};
+static_assert(sizeof(RtabCount) == 128, "a batch's counters are one 128-byte line");
+
+struct RtabDesc {
+    unsigned long long* head;   // [kRtabHeadWords]
+    RtabBatch* batches;         // [max_batches]
+    RtabCount* bcount;          // [max_batches]
+    unsigned long long* slots;  // [nslots] four words each
+    uint64_t nslots;            // a power of two
+    uint64_t key_cap;
+    uint32_t batch;             // the batch added or queried
+    uint32_t n_batches;         // batches added so far (stats)
+    RtabBatch open;             // k_rtab_open: the descriptor to write
+    // a live query's outputs
+    uint2* winner;              // nullable: {batch, record}
+    uint2* live;                // {record, 0}
+    uint64_t lcap;
+    uint64_t* n_live;
+    ramcrc_resolve_counts* counts_out;
+    uint64_t* tile_sum;         // [tiles] live tombstones << 32 | live objects, then the exclusive sums
+    ramcrc_replay_table_stats* stats_out;
+    uint32_t* ctx_status;
+};
+
+#define RTAB_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+__device__ __forceinline__ unsigned long long* rtab_word(const RtabDesc& a, uint64_t s, uint32_t w)
+{
+    return a.slots + kRtabSlotWords * s + w;
+}
+
+// Spoiled?  The word is only ever set, and a launch that sees it set late has
+// only worked on a table nobody reads any more.
+__device__ __forceinline__ bool rtab_refused(const RtabDesc& a)
+{
+    return __hip_atomic_load(&a.head[kRtabRefuse], RTAB_RLX) != 0;
+}
+
+__device__ __forceinline__ void rtab_refuse(const RtabDesc& a)
+{
+    __hip_atomic_store(&a.head[kRtabRefuse], 1ull, RTAB_RLX);
+    atomicOr(a.ctx_status, kStatusSticky);
+}
+
+// After the insert: spoiled before this add, by it, or past the key capacity?
+__device__ __forceinline__ bool rtab_spoiled_after_insert(const RtabDesc& a)
+{
+    return rtab_refused(a) || a.head[kRtabKeys] > a.key_cap;
+}
+
+__device__ __forceinline__ uint64_t rtab_n_records(const RtabBatch& b)
+{
+    const uint64_t nw = *b.n_entries;
+    return nw < b.ecap ? nw : b.ecap;
+}
+
+// The rank of record {batch, record}: a tombstone before an object, then the
+// lowest batch, then the lowest record.
+__device__ __forceinline__ uint64_t rtab_rank(uint32_t type, uint32_t batch, uint64_t record)
+{
+    return (uint64_t(type == RAMCRC_LOG_ENTRY_TYPE_OBJ) << 48) | (uint64_t(batch) << 32) | record;
+}
+
+// The key of record j of batch b, which claimed a slot and so is a participant.
+__device__ __forceinline__ ResKey rtab_key_of(const RtabBatch& b, uint64_t j)
+{
+    const u32x4 r = b.entries[j];
+    const uint64_t pay = uint64_t(r.y) + 1 + ((r.w >> 6) & 3) + 1;
+    const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
+    const ramcrc_part::Parsed p = ramcrc_part::parse(r.w & 0x3f, r.z, true, rd);
+    return ResKey{p.table_id, rd.pay + p.key_off, p.key_len};
+}
+
+// The version of record i of batch b, a participant.
+__device__ __forceinline__ uint64_t rtab_version_of(const RtabBatch& b, const u32x4 r)
+{
+    const uint64_t pay = uint64_t(r.y) + 1 + ((r.w >> 6) & 3) + 1;
+    return ramcrc_res::version(r.w & 0x3f, PartRd{b.base + uint64_t(r.x) * b.stride + pay});
+}
+
+// ------------------------------------------------------------- k_rtab_zero
+// Create and reset: the head and every slot.
+__global__ __launch_bounds__(kPartThreads) void k_rtab_zero(RtabDesc a)
+{
+    const uint64_t nw = kRtabSlotWords * a.nslots;
+    const uint64_t nthr = uint64_t(gridDim.x) * blockDim.x;
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t < kRtabHeadWords)
+        a.head[t] = 0;
+    for (uint64_t w = t; w < nw; w += nthr)
+        a.slots[w] = 0;
+}
+
+// ------------------------------------------------------------- k_rtab_open
+__global__ void k_rtab_open(RtabDesc a)
+{
+    if (blockIdx.x || threadIdx.x || rtab_refused(a))
+        return;
+    a.batches[a.batch] = a.open;
+    a.bcount[a.batch] = RtabCount{};
+}
+
+// ----------------------------------------------------------- k_rtab_insert
+template <bool kGiven>
+__global__ __launch_bounds__(kPartThreads) void k_rtab_insert(RtabDesc a)
+{
+    if (rtab_refused(a))
+        return;
+    const RtabBatch& b = a.batches[a.batch];
+    RtabCount& cnt = a.bcount[a.batch];
+    const uint64_t ne = rtab_n_records(b);
+    const uint64_t base = b.base, stride = b.stride, nseg = b.nseg;
+    const u32x4* const entries = b.entries;
+    const ramcrc_seg_status* const status = b.status;
+    const uint64_t* const key_hash = b.key_hash;
+    uint64_t* const work = b.work;
+    const uint64_t mask = a.nslots - 1;
+    const uint64_t my_claim = uint64_t(a.batch) << 32;
+    for (uint64_t i0 = uint64_t(blockIdx.x) * kPartThreads; i0 < ne;
+         i0 += uint64_t(gridDim.x) * kPartThreads) {
+        const uint64_t i = i0 + threadIdx.x;
+        bool is_obj = false, is_tomb = false, mal = false, claimed = false;
+        if (i < ne) {
+            const u32x4 r = entries[i];
+            const uint32_t seg = r.x, type = r.w & 0x3f;
+            uint64_t slot = kResNone;
+            if (seg >= nseg) {
+                rtab_refuse(a);
+            } else if (status[seg].flags & RAMCRC_SEG_OK) {
+                const uint64_t pay = uint64_t(r.y) + 1 + ((r.w >> 6) & 3) + 1;
+                const bool readable = !(r.w & kRecOverlong) && pay + r.z <= stride;
+                const PartRd rd{base + uint64_t(seg) * stride + pay};
+                if (ramcrc_res::resolved_type(type)) {
+                    const ramcrc_part::Parsed p = ramcrc_part::parse(type, r.z, readable, rd);
+                    if (p.kind == ramcrc_part::kMalformed) {
+                        mal = true;
+                    } else {
+                        is_obj = type == RAMCRC_LOG_ENTRY_TYPE_OBJ;
+                        is_tomb = !is_obj;
+                        const ResKey me{p.table_id, rd.pay + p.key_off, p.key_len};
+                        const uint64_t ver = ramcrc_res::version(type, rd);
+                        uint64_t hash;
+                        if constexpr (kGiven)
+                            hash = key_hash[i];
+                        else
+                            hash = part_key_hash(me.table_id, me.addr, me.len);
+                        // linear probing, bounded by the slot count: a table
+                        // within its key capacity has load <= 0.5, and one
+                        // past it is spoiled whether or not a slot was found
+                        uint64_t s = hash & mask;
+                        for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+                            unsigned long long c = __hip_atomic_load(rtab_word(a, s, 2), RTAB_RLX);
+                            if (c == 0 && __hip_atomic_compare_exchange_strong(
+                                              rtab_word(a, s, 2), &c,
+                                              static_cast<unsigned long long>(my_claim | (i + 1)),
+                                              __ATOMIC_RELAXED, RTAB_RLX)) {
+                                slot = s;
+                                claimed = true;
+                                break;
+                            }
+                            // c: the claimant (the failed CAS stored it), of
+                            // this batch or an earlier one; its descriptor was
+                            // written before this launch
+                            const ResKey k = rtab_key_of(a.batches[c >> 32], (c & 0xFFFFFFFFull) - 1);
+                            if (k.table_id == me.table_id && k.len == me.len &&
+                                res_bytes_equal(k.addr, me.addr, me.len)) {
+                                slot = s;
+                                break;
+                            }
+                        }
+                        if (slot != kResNone) {
+                            // a pick made below a version that raises the
+                            // maximum is stale: none, until k_rtab_pick
+                            if (__hip_atomic_fetch_max(rtab_word(a, slot, 0),
+                                                       static_cast<unsigned long long>(ver),
+                                                       RTAB_RLX) < ver)
+                                __hip_atomic_store(rtab_word(a, slot, 1), 0ull, RTAB_RLX);
+                        } else {
+                            rtab_refuse(a);   // no slot: the table is full
+                        }
+                    }
+                } else if (type == RAMCRC_LOG_ENTRY_TYPE_SAFEVERSION && readable &&
+                           r.z >= ramcrc_res::kSafeVersionBytes) {
+                    __hip_atomic_fetch_max(&a.head[kRtabSafe],
+                                           static_cast<unsigned long long>(rd.u64(0)), RTAB_RLX);
+                }
+            }
+            work[i] = slot;
+        }
+        // the counters: one atomic per wave and counter
+        const unsigned long long no = __builtin_popcountll(__ballot(is_obj));
+        const unsigned long long nt = __builtin_popcountll(__ballot(is_tomb));
+        const unsigned long long nm = __builtin_popcountll(__ballot(mal));
+        const unsigned long long nc = __builtin_popcountll(__ballot(claimed));
+        if ((threadIdx.x & (kWaveSize - 1)) == 0) {
+            if (no)
+                atomicAdd(&cnt.objects, no);
+            if (nt)
+                atomicAdd(&cnt.tombstones, nt);
+            if (nm)
+                atomicAdd(&cnt.malformed, nm);
+            if (nc)
+                atomicAdd(&a.head[kRtabKeys], nc);
+        }
+    }
+}
+
+// ------------------------------------------------------------- k_rtab_pick
+// The slots' version maxima are final for this add.
+__global__ __launch_bounds__(kPartThreads) void k_rtab_pick(RtabDesc a)
+{
+    if (rtab_spoiled_after_insert(a)) {
+        // past the key capacity: this add spoils the table
+        if (blockIdx.x == 0 && threadIdx.x == 0 && !rtab_refused(a))
+            rtab_refuse(a);
+        return;
+    }
+    const RtabBatch& b = a.batches[a.batch];
+    const uint64_t ne = rtab_n_records(b);
+    const uint64_t nthr = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < ne; i += nthr) {
+        const uint64_t s = b.work[i];
+        if (s == kResNone)
+            continue;
+        const u32x4 r = b.entries[i];
+        const uint64_t ver = rtab_version_of(b, r);
+        if (ver != __hip_atomic_load(rtab_word(a, s, 0), RTAB_RLX))
+            continue;
+        const uint64_t rank = rtab_rank(r.w & 0x3f, a.batch, i);
+        __hip_atomic_fetch_max(rtab_word(a, s, 1), static_cast<unsigned long long>(~rank), RTAB_RLX);
+    }
+}
+
+// The winner of record i's key as the table stands: the pick's complement is
+// its rank.  *type_obj: is the winner an object?
+__device__ __forceinline__ uint2 rtab_winner(const RtabDesc& a, uint64_t s, bool* type_obj)
+{
+    if (s == kResNone)
+        return make_uint2(RAMCRC_RESOLVE_NONE, RAMCRC_RESOLVE_NONE);
+    const uint64_t rank = ~*rtab_word(a, s, 1);
+    *type_obj = (rank >> 48) & 1;
+    return make_uint2(uint32_t(rank >> 32) & 0xFFFFu, uint32_t(rank));
+}
+
+// ------------------------------------------------------------ k_rtab_tiles
+__global__ __launch_bounds__(kPartThreads) void k_rtab_tiles(RtabDesc a)
+{
+    __shared__ uint64_t wsum[kPartThreads / kWaveSize];
+    if (rtab_refused(a))
+        return;
+    const RtabBatch& b = a.batches[a.batch];
+    const uint64_t ne = rtab_n_records(b);
+    const uint64_t ntiles = (ne + kPartTile - 1) / kPartTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t i0 = tile * kPartTile + uint64_t(threadIdx.x) * kPartPer;
+        uint64_t v = 0;   // live tombstones << 32 | live objects
+#pragma unroll
+        for (uint32_t k = 0; k < kPartPer; k++) {
+            const uint64_t i = i0 + k;
+            if (i >= ne)
+                continue;
+            bool obj = false;
+            const uint2 w = rtab_winner(a, b.work[i], &obj);
+            if (a.winner)
+                a.winner[i] = w;
+            if (w.x == a.batch && w.y == uint32_t(i))
+                v += obj ? 1ull : 1ull << 32;
+        }
+        uint64_t tot;
+        (void)part_block_excl(v, wsum, &tot);
+        if (threadIdx.x == 0)
+            a.tile_sum[tile] = tot;
+    }
+}
+
+// ------------------------------------------------------------- k_rtab_scan
+// One workgroup: the tile sums become exclusive sums (both halves: neither
+// reaches 2^32), kPartThreads tiles a step; then the list's length and the
+// counters.
+__global__ __launch_bounds__(kPartThreads) void k_rtab_scan(RtabDesc a)
+{
+    __shared__ uint64_t wsum[kPartThreads / kWaveSize];
+    if (rtab_refused(a)) {
+        if (threadIdx.x == 0) {
+            *a.n_live = 0;
+            *a.counts_out = ramcrc_resolve_counts{0, 0, 0, 0, 0, 0};
+        }
+        return;
+    }
+    const RtabBatch& b = a.batches[a.batch];
+    const uint64_t ne = rtab_n_records(b);
+    const uint64_t ntiles = (ne + kPartTile - 1) / kPartTile;
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += kPartThreads) {
+        const uint64_t t = t0 + threadIdx.x;
+        const uint64_t v = t < ntiles ? a.tile_sum[t] : 0ull;
+        uint64_t tot;
+        const uint64_t ex = part_block_excl(v, wsum, &tot);
+        if (t < ntiles)
+            a.tile_sum[t] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) {
+        *a.n_live = (carry & 0xFFFFFFFFull) + (carry >> 32);
+        const RtabCount& cnt = a.bcount[a.batch];
+        *a.counts_out = ramcrc_resolve_counts{cnt.objects, cnt.tombstones, carry & 0xFFFFFFFFull,
+                                              carry >> 32, cnt.malformed, a.head[kRtabSafe]};
+    }
+}
+
+// ------------------------------------------------------------- k_rtab_emit
+__global__ __launch_bounds__(kPartThreads) void k_rtab_emit(RtabDesc a)
+{
+    __shared__ uint64_t wsum[kPartThreads / kWaveSize];
+    if (rtab_refused(a))
+        return;
+    const RtabBatch& b = a.batches[a.batch];
+    const uint64_t ne = rtab_n_records(b);
+    const uint64_t ntiles = (ne + kPartTile - 1) / kPartTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t i0 = tile * kPartTile + uint64_t(threadIdx.x) * kPartPer;
+        bool live[kPartPer];
+        uint64_t v = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kPartPer; k++) {
+            live[k] = false;
+            if (i0 + k < ne) {
+                bool obj = false;
+                const uint2 w = rtab_winner(a, b.work[i0 + k], &obj);
+                live[k] = w.x == a.batch && w.y == uint32_t(i0 + k);
+            }
+            v += live[k];
+        }
+        uint64_t tot;
+        const uint64_t before = a.tile_sum[tile];
+        uint64_t dst = (before & 0xFFFFFFFFull) + (before >> 32) + part_block_excl(v, wsum, &tot);
+#pragma unroll
+        for (uint32_t k = 0; k < kPartPer; k++) {
+            if (!live[k])
+                continue;
+            if (dst < a.lcap)
+                a.live[dst] = make_uint2(uint32_t(i0 + k), 0u);
+            dst++;
+        }
+    }
+}
+
+// ------------------------------------------------------------ k_rtab_stats
+// One pass over the slots into *stats_out, which the caller zeroed: a claimed
+// slot is a key, and after an add every key has a pick.
+__global__ __launch_bounds__(kPartThreads) void k_rtab_stats(RtabDesc a)
+{
+    ramcrc_replay_table_stats* const st = a.stats_out;
+    if (rtab_refused(a)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            st->spoiled = 1;
+        return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->safe_version = a.head[kRtabSafe];
+        st->batches = a.n_batches;
+    }
+    for (uint64_t s0 = uint64_t(blockIdx.x) * kPartThreads; s0 < a.nslots;
+         s0 += uint64_t(gridDim.x) * kPartThreads) {
+        const uint64_t s = s0 + threadIdx.x;
+        bool key = false, obj = false;
+        if (s < a.nslots && *rtab_word(a, s, 2)) {
+            key = true;
+            obj = (~*rtab_word(a, s, 1) >> 48) & 1;
+        }
+        const unsigned long long nk = __builtin_popcountll(__ballot(key));
+        const unsigned long long no = __builtin_popcountll(__ballot(key && obj));
+        if ((threadIdx.x & (kWaveSize - 1)) == 0 && nk) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(&st->keys), nk);
+            if (no)
+                atomicAdd(reinterpret_cast<unsigned long long*>(&st->live_objects), no);
+            if (nk - no)
+                atomicAdd(reinterpret_cast<unsigned long long*>(&st->live_tombstones), nk - no);
+        }
+    }
+}
+
+#undef RTAB_RLX
+
+}  // namespace

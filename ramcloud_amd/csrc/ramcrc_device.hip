@@ -43,6 +43,8 @@
 //    with their certificates.
 //  * k_res_* -- which replayed objects and tombstones a recovery master keeps
 //    (DESIGN.md 5.10).
+//  * k_rtab_* -- the same decision batch by batch, in a table that outlives
+//    the call.
 //
 // The kernels live in per-family parts included below, in this order, into
 // this one translation unit (shared __device__ tables and LDS layouts, no
@@ -58,6 +60,7 @@
 //   dev_append.inc   k_app_mark, k_app_scan, k_app_copy (recovery-segment append)
 //   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
 //   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
+//   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -97,6 +100,7 @@ using ramcrc::OpTable;
 #include "dev_append.inc"
 #include "dev_partition.inc"
 #include "dev_resolve.inc"
+#include "dev_replay_table.inc"
 
 extern "C" {
 
@@ -1169,6 +1173,208 @@ int ramcrc_replay_resolve_device(ramcrc_ctx* c, const void* d_base, uint64_t seg
     hipLaunchKernelGGL(k_res_scan, dim3(1), dim3(kPartThreads), 0, s, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_res_emit, grid_of(entries_cap, kPartTile), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+struct ramcrc_replay_table {
+    ramcrc_ctx* ctx = nullptr;
+    std::mutex mu;              // serialises the calls on this table
+    unsigned long long* mem = nullptr;   // the head, the descriptors, the batches' counters, the slots
+    uint64_t key_cap = 0, nslots = 0;
+    uint32_t max_batches = 0;
+    std::vector<uint64_t> ecap;   // entries_cap of every batch added since the last reset
+};
+
+namespace {
+RtabDesc rtab_desc(const ramcrc_replay_table* t)
+{
+    RtabDesc a{};
+    a.head = t->mem;
+    a.batches = reinterpret_cast<RtabBatch*>(t->mem + kRtabHeadWords);
+    a.bcount = reinterpret_cast<RtabCount*>(a.batches + t->max_batches);
+    a.slots = reinterpret_cast<unsigned long long*>(a.bcount + t->max_batches);
+    a.nslots = t->nslots;
+    a.key_cap = t->key_cap;
+    a.n_batches = uint32_t(t->ecap.size());
+    a.ctx_status = t->ctx->status;
+    return a;
+}
+
+// Workgroups for `items` at `per` a workgroup: at most 8 per CU, at least one.
+uint32_t rtab_grid(const ramcrc_ctx* c, uint64_t items, uint64_t per)
+{
+    const uint64_t cap_grid = uint64_t(8) * c->ncu;
+    const uint64_t gr = (items + per - 1) / per;
+    return uint32_t(gr < 1 ? 1 : (gr > cap_grid ? cap_grid : gr));
+}
+}  // namespace
+
+int ramcrc_replay_table_create(ramcrc_ctx* c, uint64_t key_cap, uint32_t max_batches,
+                               ramcrc_replay_table** out)
+{
+    if (!out)
+        return RAMCRC_EINVAL;
+    *out = nullptr;
+    if (!c || key_cap >= 0xFFFFFFFFull || max_batches == 0 || max_batches > RAMCRC_REPLAY_TABLE_MAX_BATCHES)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    ramcrc_replay_table* t = new (std::nothrow) ramcrc_replay_table();
+    if (!t)
+        return RAMCRC_ENOMEM;
+    t->ctx = c;
+    t->key_cap = key_cap;
+    t->nslots = ramcrc_res::slots_for(key_cap);
+    t->max_batches = max_batches;
+    const uint64_t words =
+        kRtabHeadWords + ((sizeof(RtabBatch) + sizeof(RtabCount)) / 8) * max_batches +
+        kRtabSlotWords * t->nslots;
+    if (hipMalloc(reinterpret_cast<void**>(&t->mem), words * 8) != hipSuccess) {
+        delete t;
+        return RAMCRC_ENOMEM;
+    }
+    if (hipMemset(t->mem, 0, words * 8) != hipSuccess) {
+        (void)hipFree(t->mem);
+        delete t;
+        return RAMCRC_EHIP;
+    }
+    *out = t;
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_destroy(ramcrc_replay_table* t)
+{
+    if (!t)
+        return RAMCRC_OK;
+    {
+        DeviceGuard g(t->ctx->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(t->mem);
+    }
+    delete t;
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_reset(ramcrc_replay_table* t, void* stream)
+{
+    if (!t)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    const RtabDesc a = rtab_desc(t);
+    hipLaunchKernelGGL(k_rtab_zero, dim3(rtab_grid(c, kRtabSlotWords * t->nslots, kPartThreads)),
+                       dim3(kPartThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
+    HIPCHK(hipGetLastError());
+    t->ecap.clear();
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_add_device(ramcrc_replay_table* t, const void* d_base, uint64_t seg_stride,
+                                   uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                   const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                   const uint64_t* d_n_entries, const uint64_t* d_key_hash,
+                                   uint64_t* d_work, uint32_t* batch, void* stream)
+{
+    if (!t || n_seg >= 0xFFFFFFFFull || entries_cap >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (!d_n_entries || (n_seg && (!d_base || !d_status)) ||
+        (entries_cap && (!d_entries || !d_work)))
+        return RAMCRC_EINVAL;
+    const uint64_t B = reinterpret_cast<uint64_t>(d_base);
+    if ((B & 15) || (seg_stride & 15) || (seg_stride && n_seg > UINT64_MAX / seg_stride))
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    if (t->ecap.size() >= t->max_batches)
+        return RAMCRC_EINVAL;
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RtabDesc a = rtab_desc(t);
+    a.batch = uint32_t(t->ecap.size());
+    a.open.base = B;
+    a.open.stride = seg_stride;
+    a.open.nseg = n_seg;
+    a.open.status = d_status;
+    a.open.entries = reinterpret_cast<const u32x4*>(d_entries);
+    a.open.n_entries = d_n_entries;
+    a.open.ecap = entries_cap;
+    a.open.key_hash = d_key_hash;
+    a.open.work = d_work;
+    // the descriptor travels in the kernel's arguments: the add stays
+    // capturable and no host memory has to outlive the call
+    hipLaunchKernelGGL(k_rtab_open, dim3(1), dim3(kWaveSize), 0, s, a);
+    HIPCHK(hipGetLastError());
+    t->ecap.push_back(entries_cap);
+    if (batch)
+        *batch = a.batch;
+    const dim3 grid(rtab_grid(c, entries_cap, kPartThreads));
+    if (d_key_hash)
+        hipLaunchKernelGGL(k_rtab_insert<true>, grid, dim3(kPartThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_rtab_insert<false>, grid, dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rtab_pick, grid, dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_live_device(ramcrc_replay_table* t, uint32_t batch,
+                                    ramcrc_replay_ref* d_winner, ramcrc_placement* d_live,
+                                    uint64_t live_cap, uint64_t* d_n_live,
+                                    ramcrc_resolve_counts* d_counts, void* stream)
+{
+    if (!t || !d_n_live || !d_counts || live_cap >= 0xFFFFFFFFull || (live_cap && !d_live))
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    if (batch >= t->ecap.size())
+        return RAMCRC_EINVAL;
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t ecap = t->ecap[batch];
+    // the tile sums: the group prefixes, sized as ramcrc_ctx_reserve sizes them
+    int rc = grow_device(reinterpret_cast<void**>(&c->group_pref), &c->group_cap,
+                         (ecap + kThreads - 1) / kThreads + 1, sizeof(uint64_t));
+    if (rc)
+        return rc;
+    RtabDesc a = rtab_desc(t);
+    a.batch = batch;
+    a.winner = reinterpret_cast<uint2*>(d_winner);
+    a.live = reinterpret_cast<uint2*>(d_live);
+    a.lcap = live_cap;
+    a.n_live = d_n_live;
+    a.counts_out = d_counts;
+    a.tile_sum = c->group_pref;
+    const dim3 grid(rtab_grid(c, ecap, kPartTile));
+    hipLaunchKernelGGL(k_rtab_tiles, grid, dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rtab_scan, dim3(1), dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rtab_emit, grid, dim3(kPartThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_stats_device(ramcrc_replay_table* t, ramcrc_replay_table_stats* d_stats,
+                                     void* stream)
+{
+    if (!t || !d_stats)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RtabDesc a = rtab_desc(t);
+    a.stats_out = d_stats;
+    HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(*d_stats), s));
+    hipLaunchKernelGGL(k_rtab_stats, dim3(rtab_grid(c, t->nslots, kPartThreads)), dim3(kPartThreads),
+                       0, s, a);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }

@@ -18,6 +18,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <new>
+#include <vector>
+
 #include "gf2.h"
 #include "murmur3.h"
 #include "partition_rules.h"
@@ -566,6 +569,231 @@ int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n
     free(slots);
     *n_live = nl;
     *counts = ct;
+    return RAMCRC_OK;
+}
+
+// ----------------------------------------------------------------------------
+// The persistent replay table on the host (ramcrc_replay_table_*_host): the
+// one-call's pass, one batch at a time into a table that stays.  A slot keeps
+// its claimant's key fields (pointers into the caller's segments, which the
+// lifetime rule keeps valid) and the key's winner so far.
+struct ramcrc_replay_table_host {
+    struct Slot {
+        uint64_t claim;   // batch << 32 | record + 1 of the claimant, 0: empty
+        uint64_t table_id;
+        const uint8_t* key;
+        uint32_t key_len;
+        uint64_t version, rank;   // the winner so far (rank: is_object << 48 | batch << 32 | record)
+    };
+    struct Batch {
+        const uint64_t* work;
+        uint64_t n;
+        uint64_t objects, tombstones, malformed;
+    };
+    uint64_t key_cap = 0, keys = 0, safe_version = 0;
+    uint32_t max_batches = 0;
+    bool spoiled = false;
+    std::vector<Slot> slots;
+    std::vector<Batch> batches;
+};
+
+int ramcrc_replay_table_create_host(uint64_t key_cap, uint32_t max_batches,
+                                    ramcrc_replay_table_host** out)
+{
+    if (!out)
+        return RAMCRC_EINVAL;
+    *out = nullptr;
+    if (key_cap >= 0xFFFFFFFFull || max_batches == 0 || max_batches > RAMCRC_REPLAY_TABLE_MAX_BATCHES)
+        return RAMCRC_EINVAL;
+    try {
+        ramcrc_replay_table_host* t = new ramcrc_replay_table_host();
+        t->key_cap = key_cap;
+        t->max_batches = max_batches;
+        try {
+            t->slots.assign(ramcrc_res::slots_for(key_cap), ramcrc_replay_table_host::Slot{});
+        } catch (...) {
+            delete t;
+            throw;
+        }
+        *out = t;
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_destroy_host(ramcrc_replay_table_host* t)
+{
+    delete t;
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_reset_host(ramcrc_replay_table_host* t)
+{
+    if (!t)
+        return RAMCRC_EINVAL;
+    t->slots.assign(t->slots.size(), ramcrc_replay_table_host::Slot{});
+    t->batches.clear();
+    t->keys = t->safe_version = 0;
+    t->spoiled = false;
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_add_host(ramcrc_replay_table_host* t, const void* base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* status,
+                                 const ramcrc_seg_entry* entries, uint64_t n_entries,
+                                 const uint64_t* key_hash, uint64_t* work, uint32_t* batch)
+{
+    namespace rp = ramcrc_part;
+    namespace rr = ramcrc_res;
+    if (!t || n_seg >= 0xFFFFFFFFull || n_entries >= 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if ((n_seg && (!base || !status)) || (n_entries && (!entries || !work)))
+        return RAMCRC_EINVAL;
+    if (seg_stride && n_seg > UINT64_MAX / seg_stride)
+        return RAMCRC_EINVAL;
+    if (t->batches.size() >= t->max_batches)
+        return RAMCRC_EINVAL;
+    const uint64_t bno = t->batches.size();
+    try {
+        t->batches.push_back(ramcrc_replay_table_host::Batch{work, n_entries, 0, 0, 0});
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    if (batch)
+        *batch = uint32_t(bno);
+    if (t->spoiled)
+        return RAMCRC_EINVAL;
+    for (uint64_t i = 0; i < n_entries; i++)
+        if (entries[i].segment >= n_seg) {
+            t->spoiled = true;
+            return RAMCRC_EINVAL;
+        }
+    struct Rd {
+        const uint8_t* pay;
+        uint32_t u8(uint32_t o) const { return pay[o]; }
+        uint32_t u16(uint32_t o) const { return ld16(pay + o); }
+        uint32_t u32(uint32_t o) const { return ld32(pay + o); }
+        uint64_t u64(uint32_t o) const { return ld64(pay + o); }
+    };
+    ramcrc_replay_table_host::Batch& bt = t->batches.back();
+    const uint8_t* const b = static_cast<const uint8_t*>(base);
+    const uint64_t mask = t->slots.size() - 1;
+    for (uint64_t i = 0; i < n_entries; i++) {
+        const ramcrc_seg_entry& r = entries[i];
+        const uint32_t type = r.header & 0x3f;
+        work[i] = ~0ull;
+        if (!(status[r.segment].flags & RAMCRC_SEG_OK))
+            continue;
+        const uint64_t pay = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+        const bool readable = !(r.header & RAMCRC_SEG_ENTRY_OVERLONG) && pay + r.length <= seg_stride;
+        const Rd rd{b + r.segment * seg_stride + pay};
+        if (type == RAMCRC_LOG_ENTRY_TYPE_SAFEVERSION) {
+            if (readable && r.length >= rr::kSafeVersionBytes && rd.u64(0) > t->safe_version)
+                t->safe_version = rd.u64(0);
+            continue;
+        }
+        if (!rr::resolved_type(type))
+            continue;
+        const rp::Parsed p = rp::parse(type, r.length, readable, rd);
+        if (p.kind == rp::kMalformed) {
+            bt.malformed++;
+            continue;
+        }
+        const bool is_obj = type == RAMCRC_LOG_ENTRY_TYPE_OBJ;
+        (is_obj ? bt.objects : bt.tombstones)++;
+        const uint8_t* const key = rd.pay + p.key_off;
+        const uint64_t version = rr::version(type, rd);
+        const uint64_t rank = (uint64_t(is_obj) << 48) | (bno << 32) | i;
+        const uint64_t hash = key_hash ? key_hash[i] : ramcrc::key_hash(p.table_id, key, p.key_len);
+        uint64_t s = hash & mask, step = 0;
+        for (; step <= mask; step++, s = (s + 1) & mask) {
+            ramcrc_replay_table_host::Slot& sl = t->slots[s];
+            if (!sl.claim) {
+                sl.claim = (bno << 32) | (i + 1);
+                sl.table_id = p.table_id;
+                sl.key = key;
+                sl.key_len = p.key_len;
+                sl.version = version;
+                sl.rank = rank;
+                t->keys++;
+                break;
+            }
+            if (sl.table_id != p.table_id || sl.key_len != p.key_len ||
+                (p.key_len && memcmp(sl.key, key, p.key_len)))
+                continue;
+            if (rr::beats(version, rank, sl.version, sl.rank)) {
+                sl.version = version;
+                sl.rank = rank;
+            }
+            break;
+        }
+        if (step > mask) {   // no slot: the table is full
+            t->spoiled = true;
+            return RAMCRC_EINVAL;
+        }
+        work[i] = s;
+    }
+    if (t->keys > t->key_cap) {
+        t->spoiled = true;
+        return RAMCRC_EINVAL;
+    }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_live_host(ramcrc_replay_table_host* t, uint32_t batch,
+                                  ramcrc_replay_ref* winner, ramcrc_placement* live,
+                                  uint64_t live_cap, uint64_t* n_live, ramcrc_resolve_counts* counts)
+{
+    if (!t || !n_live || !counts || live_cap >= 0xFFFFFFFFull || (live_cap && !live) ||
+        batch >= t->batches.size())
+        return RAMCRC_EINVAL;
+    *n_live = 0;
+    *counts = ramcrc_resolve_counts{0, 0, 0, 0, 0, 0};
+    if (t->spoiled)
+        return RAMCRC_OK;
+    const ramcrc_replay_table_host::Batch& bt = t->batches[batch];
+    ramcrc_resolve_counts ct{bt.objects, bt.tombstones, 0, 0, bt.malformed, t->safe_version};
+    uint64_t nl = 0;
+    for (uint64_t i = 0; i < bt.n; i++) {
+        ramcrc_replay_ref w{0xFFFFFFFFu, 0xFFFFFFFFu};
+        bool obj = false;
+        if (bt.work[i] != ~0ull) {
+            const uint64_t rank = t->slots[bt.work[i]].rank;
+            w = ramcrc_replay_ref{uint32_t(rank >> 32) & 0xFFFFu, uint32_t(rank)};
+            obj = (rank >> 48) & 1;
+        }
+        if (winner)
+            winner[i] = w;
+        if (w.batch != batch || w.record != i)
+            continue;
+        (obj ? ct.live_objects : ct.live_tombstones)++;
+        if (nl < live_cap)
+            live[nl] = ramcrc_placement{uint32_t(i), 0u};
+        nl++;
+    }
+    *n_live = nl;
+    *counts = ct;
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_table_stats* stats)
+{
+    if (!t || !stats)
+        return RAMCRC_EINVAL;
+    *stats = ramcrc_replay_table_stats{0, 0, 0, 0, 0, 0};
+    if (t->spoiled) {
+        stats->spoiled = 1;
+        return RAMCRC_OK;
+    }
+    for (const ramcrc_replay_table_host::Slot& sl : t->slots) {
+        if (!sl.claim)
+            continue;
+        stats->keys++;
+        ((sl.rank >> 48) & 1 ? stats->live_objects : stats->live_tombstones)++;
+    }
+    stats->safe_version = t->safe_version;
+    stats->batches = t->batches.size();
     return RAMCRC_OK;
 }
 

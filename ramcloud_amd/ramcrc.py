@@ -100,6 +100,20 @@ def lib():
                                                vp, vp, vp]),
         "ramcrc_replay_resolve_host": (i32, [vp, u64, u64, vp, vp, u64, vp, vp, vp, u64,
                                              _c.POINTER(u64), vp]),
+        "ramcrc_replay_table_create": (i32, [vp, u64, u32, _c.POINTER(vp)]),
+        "ramcrc_replay_table_destroy": (i32, [vp]),
+        "ramcrc_replay_table_reset": (i32, [vp, vp]),
+        "ramcrc_replay_table_add_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, vp,
+                                                 _c.POINTER(u32), vp]),
+        "ramcrc_replay_table_live_device": (i32, [vp, u32, vp, vp, u64, vp, vp, vp]),
+        "ramcrc_replay_table_stats_device": (i32, [vp, vp, vp]),
+        "ramcrc_replay_table_create_host": (i32, [u64, u32, _c.POINTER(vp)]),
+        "ramcrc_replay_table_destroy_host": (i32, [vp]),
+        "ramcrc_replay_table_reset_host": (i32, [vp]),
+        "ramcrc_replay_table_add_host": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp,
+                                               _c.POINTER(u32)]),
+        "ramcrc_replay_table_live_host": (i32, [vp, u32, vp, vp, u64, _c.POINTER(u64), vp]),
+        "ramcrc_replay_table_stats_host": (i32, [vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -335,6 +349,89 @@ def replay_resolve_host(segments, seg_stride, n_seg, status, entries, key_hash=N
                                           p(counts))
     _check(rc, "ramcrc_replay_resolve_host")
     return winner, live[:min(need.value, cap)], need.value, counts[0]
+
+
+class ReplayTableHost:
+    """The persistent replay table on the host (ramcrc_replay_table_*_host):
+    replay_resolve_host's decision fed batch by batch.  The table keeps the
+    arrays of every added batch alive until reset() or close()."""
+
+    def __init__(self, key_cap, max_batches):
+        h = _c.c_void_p()
+        _check(lib().ramcrc_replay_table_create_host(int(key_cap), int(max_batches), _c.byref(h)),
+               "ramcrc_replay_table_create_host")
+        self._h = h
+        self._keep = []
+
+    def close(self):
+        if self._h:
+            lib().ramcrc_replay_table_destroy_host(self._h)
+            self._h = None
+            self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(lib().ramcrc_replay_table_reset_host(self._h), "ramcrc_replay_table_reset_host")
+        self._keep = []
+
+    def add(self, segments, seg_stride, n_seg, status, entries, key_hash=None):
+        """Resolve one walk's records into the table; arrays as
+        replay_resolve_host takes them.  Returns the batch number; raises
+        RamcrcError (code EINVAL) where the device form spoils the table, on a
+        spoiled table, and past max_batches."""
+        segments = np.ascontiguousarray(segments, np.uint8)
+        status = np.ascontiguousarray(np.asarray(status).view(np.uint32)).reshape(-1, 4)
+        entries = np.ascontiguousarray(np.asarray(entries).view(np.uint32)).reshape(-1, 4)
+        n = entries.shape[0]
+        if segments.size < n_seg * seg_stride or status.shape[0] < n_seg:
+            raise RamcrcError("ReplayTableHost.add: an array is smaller than its geometry")
+        if key_hash is not None:
+            key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+            if key_hash.size < n:
+                raise RamcrcError("ReplayTableHost.add: fewer hashes than records")
+        work = np.zeros(max(n, 1), np.uint64)
+        none = 0xFFFFFFFF
+        batch = _c.c_uint32(none)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_add_host(self._h, p(segments), seg_stride, n_seg, p(status),
+                                                p(entries), n, p(key_hash), p(work),
+                                                _c.byref(batch))
+        if batch.value != none:   # the batch has a number: the table reads its arrays from now on
+            self._keep.append((segments, status, entries, key_hash, work))
+        _check(rc, "ramcrc_replay_table_add_host")
+        return batch.value
+
+    def live(self, batch, live_cap=None):
+        """The verdict on one batch as the table stands.  Returns (winner:
+        segments.REPLAY_REF_DTYPE [n], live uint32 [m, 2] with m = min(needed,
+        live_cap), needed, counts: a segments.RESOLVE_COUNTS_DTYPE scalar)."""
+        from . import segments as _seg
+        if not 0 <= int(batch) < len(self._keep):
+            raise RamcrcError("ReplayTableHost.live: no such batch", EINVAL)
+        n = self._keep[int(batch)][2].shape[0]
+        cap = n if live_cap is None else int(live_cap)
+        winner = np.zeros(n, _seg.REPLAY_REF_DTYPE)
+        live = np.zeros((cap, 2), np.uint32)
+        counts = np.zeros(1, _seg.RESOLVE_COUNTS_DTYPE)
+        need = _c.c_uint64(0)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a.size else None
+        rc = lib().ramcrc_replay_table_live_host(self._h, int(batch), p(winner), p(live), cap,
+                                                 _c.byref(need), p(counts))
+        _check(rc, "ramcrc_replay_table_live_host")
+        return winner, live[:min(need.value, cap)], need.value, counts[0]
+
+    def stats(self):
+        """A segments.REPLAY_TABLE_STATS_DTYPE scalar."""
+        from . import segments as _seg
+        st = np.zeros(1, _seg.REPLAY_TABLE_STATS_DTYPE)
+        _check(lib().ramcrc_replay_table_stats_host(self._h, _c.c_void_p(st.ctypes.data)),
+               "ramcrc_replay_table_stats_host")
+        return st[0]
 
 
 # ---------------------------------------------------------------- device
@@ -651,6 +748,77 @@ class Context:
                                       FINALIZE if finalize else 0, batch, depth)
         _check(rc, "ramcrc_stream_host")
         return out
+
+
+class ReplayTable:
+    """A replay table on the GPU that outlives a call (ramcrc_replay_table_*):
+    Context.replay_resolve's decision fed batch by batch.  Every tensor given
+    to add() must stay allocated and unchanged until reset() or close(); the
+    table holds references to them for that long.  Close it before ctx."""
+
+    def __init__(self, ctx, key_cap, max_batches):
+        h = _c.c_void_p()
+        _check(lib().ramcrc_replay_table_create(ctx._h, int(key_cap), int(max_batches),
+                                                _c.byref(h)), "ramcrc_replay_table_create")
+        self._h = h
+        self._ctx = ctx
+        self._keep = []
+
+    def close(self):
+        if self._h:
+            lib().ramcrc_replay_table_destroy(self._h)
+            self._h = None
+            self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        """Empty the table and forget its batches; stream-ordered."""
+        _check(lib().ramcrc_replay_table_reset(self._h, _stream(stream)),
+               "ramcrc_replay_table_reset")
+        self._keep = []
+
+    def add(self, data, seg_stride, nseg, status, entries, n_entries, work, key_hash=None,
+            stream=None):
+        """Resolve one walk's records into the table.  status, entries,
+        n_entries: the walk's tables; work: int64 CUDA [entries], written here
+        and read by live(); key_hash: int64 CUDA [entries] (the partition
+        call's output) or None (computed).  Returns the batch number.
+        Asynchronous; a spoiled table shows in Context.check() and stats()."""
+        ecap = 0 if entries is None else entries.shape[0]
+        if ecap and (work is None or work.numel() < ecap):
+            raise RamcrcError("ReplayTable.add: work is smaller than the record table")
+        batch = _c.c_uint32(0)
+        rc = lib().ramcrc_replay_table_add_device(
+            self._h, _ptr(data), seg_stride, nseg, _ptr(status), _ptr(entries), ecap,
+            _ptr(n_entries), _ptr(key_hash), _ptr(work), _c.byref(batch), _stream(stream))
+        _check(rc, "ramcrc_replay_table_add_device")
+        self._keep.append((data, status, entries, n_entries, key_hash, work))
+        return batch.value
+
+    def live(self, batch, live, n_live, counts, winner=None, stream=None):
+        """The verdict on one batch as the table stands now.  live: int32 CUDA
+        [cap, 2] out and n_live: int64 CUDA [1] out, as recovery_append takes
+        them with n_part = 1 over that batch's segments; counts: int64 CUDA
+        [6] out (segments.RESOLVE_COUNTS_DTYPE); winner: int32 CUDA [entries,
+        2] out (segments.REPLAY_REF_DTYPE) or None.  Asynchronous."""
+        lcap = 0 if live is None else live.shape[0]
+        rc = lib().ramcrc_replay_table_live_device(
+            self._h, int(batch), _ptr(winner), _ptr(live), lcap, _ptr(n_live), _ptr(counts),
+            _stream(stream))
+        _check(rc, "ramcrc_replay_table_live_device")
+        return live
+
+    def stats(self, stats, stream=None):
+        """The whole table into stats: int64 CUDA [6] out
+        (segments.REPLAY_TABLE_STATS_DTYPE).  Asynchronous."""
+        _check(lib().ramcrc_replay_table_stats_device(self._h, _ptr(stats), _stream(stream)),
+               "ramcrc_replay_table_stats_device")
+        return stats
 
 
 # ------------------------------------------------------------ multi-GPU shard

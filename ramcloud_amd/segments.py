@@ -46,6 +46,13 @@ RESOLVE_COUNTS_DTYPE = np.dtype([("objects", "<u8"), ("tombstones", "<u8"), ("li
                                  ("live_tombstones", "<u8"), ("malformed", "<u8"),
                                  ("safe_version", "<u8")])
 RESOLVE_NONE = 0xFFFFFFFF
+# ramcrc_replay_ref and ramcrc_replay_table_stats (ramcrc_replay_table_*); "none" is
+# {RESOLVE_NONE, RESOLVE_NONE}
+REPLAY_REF_DTYPE = np.dtype([("batch", "<u4"), ("record", "<u4")])
+REPLAY_TABLE_STATS_DTYPE = np.dtype([("keys", "<u8"), ("live_objects", "<u8"),
+                                     ("live_tombstones", "<u8"), ("safe_version", "<u8"),
+                                     ("batches", "<u8"), ("spoiled", "<u8")])
+REPLAY_TABLE_MAX_BATCHES = 65536
 LOG_ENTRY_TYPE_SEGHEADER = 1    # src/LogEntryTypes.h:32
 LOG_ENTRY_TYPE_RPCRESULT = 7    # src/LogEntryTypes.h:50
 LOG_ENTRY_TYPE_OBJ = 2          # src/LogEntryTypes.h:35
