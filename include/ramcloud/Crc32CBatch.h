@@ -242,6 +242,41 @@ class Crc32CBatch {
     }
 
     /**
+     * On a recovery master: what ObjectManager::replaySegment hands to
+     * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,
+     * :840-867).  d_live / d_nLive is deviceReplayResolve's or
+     * ReplayTable::live's list; side-log segment k lies at d_out + k *
+     * outStride, holds outCapacity bytes and receives the kept records of
+     * replica k as deviceRecoveryAppend with one partition writes them, except
+     * that every kept tombstone leaves as the reference rewrites it (:845-851):
+     * segmentId 0, `timestamp` (one WallTime::secondsTimestamp() per call),
+     * and ObjectTombstone::computeChecksum over the new bytes.  d_refs
+     * (nullable) receives for placement i the Log::Reference of its record --
+     * {side-log segment, offset of the entry header} -- for the hash table's
+     * replace(), or RAMCRC_LOG_REF_NONE twice when it was not appended;
+     * d_counts the append counts and byte sums: see
+     * ramcrc_replay_sidelog_device.  Returns after the kernels finished on
+     * `stream`; throws when the list was refused (nothing is written then).
+     */
+    void
+    deviceReplaySideLog(const void* d_base, uint64_t stride, uint64_t count,
+                        const ramcrc_seg_status* d_status, const ramcrc_seg_entry* d_entries,
+                        uint64_t entriesCap, const uint64_t* d_nEntries,
+                        const ramcrc_placement* d_live, uint64_t liveCap, const uint64_t* d_nLive,
+                        uint32_t timestamp, void* d_out, uint64_t outStride, uint32_t outCapacity,
+                        ramcrc_seg_cert* d_outCerts, ramcrc_append_status* d_outStatus,
+                        ramcrc_log_ref* d_refs, ramcrc_sidelog_counts* d_counts,
+                        void* stream = NULL)
+    {
+        check(ramcrc_replay_sidelog_device(context(), d_base, stride, count, d_status, d_entries,
+                                           entriesCap, d_nEntries, d_live, liveCap, d_nLive,
+                                           timestamp, d_out, outStride, outCapacity, d_outCerts,
+                                           d_outStatus, d_refs, d_counts, stream),
+              "ramcrc_replay_sidelog_device");
+        sync(stream);
+    }
+
+    /**
      * Object::assembleForLog's checksum for a batch of serialized objects
      * (the write path, src/ObjectManager.cc:1274): header.checksum of every
      * object (Object::Header + keysAndValue, src/Object.h:137-182) is set to

@@ -496,8 +496,8 @@ int ramcrc_recovery_partition_host(const void* base, uint64_t seg_stride, uint64
  * sequential replay synthesizes for an object it overwrites (:697-717,
  * :804-835); and insertion into the master's table.  A surviving tombstone is
  * listed as it lies in its segment: the reference rewrites its segment id,
- * timestamp and checksum before it logs it (:845-851), which remains the
- * caller's job. */
+ * timestamp and checksum before it logs it (:845-851); that rewrite is
+ * ramcrc_replay_sidelog_device's, which takes this call's live list. */
 #define RAMCRC_RESOLVE_NONE 0xFFFFFFFFu
 typedef struct ramcrc_resolve_counts {
     uint64_t objects, tombstones;            /* participants */
@@ -597,9 +597,10 @@ int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n
  * table per add, and is not made.
  *
  * Not done, as in the one-call: the synthesized tombstone for an overwritten
- * object (:697-717, :804-835), raiseSafeVersion(version + 1) (:797), the
- * rewrite of a kept tombstone's header, PREP and the other transaction
- * records, and insertion into the master's own table.
+ * object (:697-717, :804-835), raiseSafeVersion(version + 1) (:797), PREP and
+ * the other transaction records, and insertion into the master's own table.
+ * The rewrite of a kept tombstone's header is ramcrc_replay_sidelog_device's,
+ * below.
  *
  * Concurrency.  All calls are stream-ordered and asynchronous; calls on one
  * table are serialised by the handle; a caller who uses several streams
@@ -683,6 +684,107 @@ int ramcrc_replay_table_live_host(ramcrc_replay_table_host* t, uint32_t batch,
                                   uint64_t live_cap, uint64_t* n_live,
                                   ramcrc_resolve_counts* counts);
 int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_table_stats* stats);
+
+/* The side log of a replay: what ObjectManager::replaySegment hands to
+ * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,
+ * :840-867), and where each record then lies.  The call is
+ * ramcrc_recovery_append_device at n_part = 1 over a live list -- the {record,
+ * 0} lists ramcrc_replay_resolve_device and ramcrc_replay_table_live_device
+ * write -- with two additions: kept tombstones are rewritten as the reference
+ * rewrites them before it logs them, and every placement gets a reference.
+ *
+ * Append rules.  Every rule of ramcrc_recovery_append_device at n_part = 1
+ * holds unchanged: output k belongs to source segment k; entry header bytes,
+ * the fit rule, d_out_certs and d_out_status, "bytes of an output at or past
+ * its head are never written", the alignment rules (d_base 16-byte aligned,
+ * seg_stride a multiple of 16, d_out and out_stride free, out_stride >=
+ * out_capacity, live_cap < 2^32, outputs not overlapping the source),
+ * stream-ordered and asynchronous.  A placement whose partition is not 0 is a
+ * partition >= n_part: the call refuses.
+ *
+ * Refusal.  The conditions are the append's; a refused call writes none of
+ * d_out, d_out_certs, d_out_status, d_refs, d_counts, and ramcrc_ctx_check
+ * returns RAMCRC_EREFUSED.  With n_seg = 0 the call returns RAMCRC_OK and
+ * writes nothing, as the append does.
+ *
+ * Tombstones.  An appended record of type OBJTOMB whose payload has at least
+ * 32 bytes (ObjectTombstone::Header, src/Object.h:285-338) is written with
+ *   payload [8, 16)  zero: segmentId 0, "can be cleaned as soon as the hash
+ *                    table ceases to reference it" (:847-849);
+ *   payload [24, 28) `timestamp`, little-endian (:845);
+ *   payload [28, 32) the finalized CRC32C of the new bytes [0, 28) followed
+ *                    by the key [32, length): ObjectTombstone::computeChecksum
+ *                    (src/Object.cc:1042-1057), little-endian (:850-851);
+ * and every other payload byte copied.  The checksum is computed from the
+ * bytes, not derived from the stored one: a tombstone whose stored checksum
+ * was wrong leaves with a correct one, as in the reference, where replay only
+ * warns about it (:758-763).  An OBJTOMB record shorter than 32 bytes is
+ * copied unchanged and counted in short_tombstones (resolution never lists
+ * one, but the call takes any list).  Every other type is copied byte for
+ * byte, exactly as the append copies it.
+ *
+ * Certificates are the append's: Segment::getAppendedLength's checksum covers
+ * entry headers and the length only (src/Segment.cc:672-684), so the rewrite
+ * of payload bytes does not change it.
+ *
+ * timestamp is passed by value: the caller reads its clock once per call, as
+ * one WallTime::secondsTimestamp() would serve a segment.  A captured graph
+ * replays the captured value.
+ *
+ * d_refs (nullable; one per entry of the live list, live_cap of them):
+ * d_refs[i] = {output index, byte offset of the entry header} of the record
+ * placement i appended -- the Log::Reference sideLog->append returns, for
+ * replace(lock, key, reference) (:734, :867) -- or {0xFFFFFFFF, 0xFFFFFFFF}
+ * when the placement was not appended (its output is RAMCRC_SEG_APPEND_FULL or
+ * RAMCRC_SEG_SOURCE_BAD).  Entries at and past *d_n_live are not written.
+ * d_counts (required): see the structure.
+ *
+ * Still not done: the synthesized tombstone for an overwritten object
+ * (:697-717, :804-835), raiseSafeVersion (:797), transaction records (copied
+ * like any other type when listed), and insertion into the master's table.
+ * The intended use needs no synthesized tombstone: a master that asks for the
+ * live lists after its last add logs only final winners, so nothing it logged
+ * is ever overwritten.
+ *
+ * Scratch comes from the context: after ramcrc_ctx_reserve(ctx, 80 + 4 *
+ * n_seg, live_cap / 2 + 1), or after one call of the same shape, it does not
+ * allocate. */
+typedef struct ramcrc_log_ref {
+    uint32_t segment;   /* output index (= source segment) */
+    uint32_t offset;    /* of the entry header in that output */
+} ramcrc_log_ref;
+#define RAMCRC_LOG_REF_NONE 0xFFFFFFFFu
+
+typedef struct ramcrc_sidelog_counts {
+    uint64_t objects;           /* appended OBJ records (objectAppendCount, :742) */
+    uint64_t tombstones;        /* appended and rewritten (tombstoneAppendCount, :862) */
+    uint64_t other;             /* appended records of every other type */
+    uint64_t object_bytes;      /* payload bytes of `objects` (liveObjectBytes, TableStats: :729-743) */
+    uint64_t tombstone_bytes;   /* payload bytes of `tombstones` (TableStats: :863-866) */
+    uint64_t short_tombstones;  /* appended OBJTOMB records below 32 bytes: copied unchanged */
+    uint64_t left_out;          /* placements not appended */
+} ramcrc_sidelog_counts;
+
+int ramcrc_replay_sidelog_device(ramcrc_ctx* ctx, const void* d_base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                 const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                 const uint64_t* d_n_entries, const ramcrc_placement* d_live,
+                                 uint64_t live_cap, const uint64_t* d_n_live, uint32_t timestamp,
+                                 void* d_out, uint64_t out_stride, uint32_t out_capacity,
+                                 ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
+                                 ramcrc_log_ref* d_refs, ramcrc_sidelog_counts* d_counts,
+                                 void* stream);
+
+/* The same on the host, single-threaded: host pointers, n_entries records,
+ * n_live placements, no alignment rules.  Returns RAMCRC_EINVAL where the
+ * device form refuses (nothing is written). */
+int ramcrc_replay_sidelog_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                               const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                               uint64_t n_entries, const ramcrc_placement* live, uint64_t n_live,
+                               uint32_t timestamp, void* out, uint64_t out_stride,
+                               uint32_t out_capacity, ramcrc_seg_cert* out_certs,
+                               ramcrc_append_status* out_status, ramcrc_log_ref* refs,
+                               ramcrc_sidelog_counts* counts);
 
 /* ObjectManager::replaySegment's checksum checks for every record of a walk
  * whose segment passed the metadata check (d_status flags RAMCRC_SEG_OK;

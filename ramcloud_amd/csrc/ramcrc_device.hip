@@ -58,6 +58,7 @@
 //   dev_walk.inc     k_seg_walk and the parallel walk (k_walk_*)
 //   dev_checks.inc   k_obj_compare, k_obj_stamp, certificate kernels
 //   dev_append.inc   k_app_mark, k_app_scan, k_app_copy (recovery-segment append)
+//   dev_sidelog.inc  k_sl_stamp (rewritten tombstones, references, counts)
 //   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
 //   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
 //   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table)
@@ -79,6 +80,7 @@
 #include "murmur3.h"
 #include "partition_rules.h"
 #include "resolve_rules.h"
+#include "sidelog_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -98,6 +100,7 @@ using ramcrc::OpTable;
 #include "dev_walk.inc"
 #include "dev_checks.inc"
 #include "dev_append.inc"
+#include "dev_sidelog.inc"
 #include "dev_partition.inc"
 #include "dev_resolve.inc"
 #include "dev_replay_table.inc"
@@ -932,14 +935,17 @@ int ramcrc_segments_certify_device(ramcrc_ctx* c, const void* d_base, uint64_t s
     return RAMCRC_OK;
 }
 
-int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
-                                  uint64_t n_seg, const ramcrc_seg_status* d_status,
-                                  const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
-                                  const uint64_t* d_n_entries, const ramcrc_placement* d_place,
-                                  uint64_t place_cap, const uint64_t* d_n_place, uint32_t n_part,
-                                  void* d_out, uint64_t out_stride, uint32_t out_capacity,
-                                  ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
-                                  void* stream)
+namespace {
+// The append's checks and launches, shared by ramcrc_recovery_append_device
+// (sl == nullptr: exactly k_app_mark, k_app_scan, k_app_copy) and
+// ramcrc_replay_sidelog_device (k_sl_stamp behind them; sl->counts is set
+// here, to a line of its own behind the append's scratch words).
+int app_launch(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride, uint64_t n_seg,
+               const ramcrc_seg_status* d_status, const ramcrc_seg_entry* d_entries,
+               uint64_t entries_cap, const uint64_t* d_n_entries, const ramcrc_placement* d_place,
+               uint64_t place_cap, const uint64_t* d_n_place, uint32_t n_part, void* d_out,
+               uint64_t out_stride, uint32_t out_capacity, ramcrc_seg_cert* d_out_certs,
+               ramcrc_append_status* d_out_status, SlDesc* sl, void* stream)
 {
     if (!c || n_part == 0 || out_stride < out_capacity || n_seg > 0xFFFFFFFFull ||
         place_cap > 0xFFFFFFFFull)
@@ -968,7 +974,9 @@ int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t se
     // placements' offsets in the plan buffer (ramcrc.h states these sizes)
     const uint64_t head_words = (4 + 3 * n_seg + 3) & ~uint64_t(3);
     const uint64_t state_words = n_part > kAppLdsParts ? n_out * (sizeof(AppState) / 4) : 0;
-    int rc = reserve_locked(c, head_words + state_words, place_cap / 2 + 1);
+    const uint64_t app_words = head_words + state_words;
+    const uint64_t sl_at = (app_words + kSlCountWords - 1) / kSlCountWords * kSlCountWords;
+    int rc = reserve_locked(c, sl ? sl_at + kSlCountWords : app_words, place_cap / 2 + 1);
     if (rc)
         return rc;
     AppDesc a{};
@@ -996,6 +1004,10 @@ int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t se
     a.states = reinterpret_cast<AppState*>(c->partials + head_words);
     a.ctx_status = c->status;
     HIPCHK(hipMemsetAsync(c->partials, 0, head_words * sizeof(uint32_t), s));
+    if (sl) {
+        sl->counts = reinterpret_cast<unsigned long long*>(c->partials + sl_at);
+        HIPCHK(hipMemsetAsync(sl->counts, 0, kSlCountWords * sizeof(uint32_t), s));
+    }
     const uint64_t cap_grid = uint64_t(8) * c->ncu;
     uint64_t gm = (place_cap + 255) / 256;
     gm = gm < 1 ? 1 : (gm > cap_grid ? cap_grid : gm);
@@ -1019,7 +1031,50 @@ int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t se
         hipLaunchKernelGGL(k_app_copy, dim3(uint32_t(gc)), dim3(kAppCopyThreads), 0, s, a);
         HIPCHK(hipGetLastError());
     }
+    if (sl) {
+        // (at least one workgroup: an empty list still gets its zero counts)
+        uint64_t gt = (place_cap + kSlThreads - 1) / kSlThreads;
+        gt = gt < 1 ? 1 : (gt > cap_grid ? cap_grid : gt);
+        hipLaunchKernelGGL(k_sl_stamp, dim3(uint32_t(gt)), dim3(kSlThreads), 0, s, a, *sl);
+        HIPCHK(hipGetLastError());
+    }
     return RAMCRC_OK;
+}
+}  // namespace
+
+int ramcrc_recovery_append_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
+                                  uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                  const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                  const uint64_t* d_n_entries, const ramcrc_placement* d_place,
+                                  uint64_t place_cap, const uint64_t* d_n_place, uint32_t n_part,
+                                  void* d_out, uint64_t out_stride, uint32_t out_capacity,
+                                  ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
+                                  void* stream)
+{
+    return app_launch(c, d_base, seg_stride, n_seg, d_status, d_entries, entries_cap, d_n_entries,
+                      d_place, place_cap, d_n_place, n_part, d_out, out_stride, out_capacity,
+                      d_out_certs, d_out_status, nullptr, stream);
+}
+
+int ramcrc_replay_sidelog_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,
+                                 uint64_t n_seg, const ramcrc_seg_status* d_status,
+                                 const ramcrc_seg_entry* d_entries, uint64_t entries_cap,
+                                 const uint64_t* d_n_entries, const ramcrc_placement* d_live,
+                                 uint64_t live_cap, const uint64_t* d_n_live, uint32_t timestamp,
+                                 void* d_out, uint64_t out_stride, uint32_t out_capacity,
+                                 ramcrc_seg_cert* d_out_certs, ramcrc_append_status* d_out_status,
+                                 ramcrc_log_ref* d_refs, ramcrc_sidelog_counts* d_counts,
+                                 void* stream)
+{
+    if (!d_counts)
+        return RAMCRC_EINVAL;
+    SlDesc sl{};
+    sl.refs = reinterpret_cast<uint2*>(d_refs);
+    sl.counts_out = d_counts;
+    sl.timestamp = timestamp;
+    return app_launch(c, d_base, seg_stride, n_seg, d_status, d_entries, entries_cap, d_n_entries,
+                      d_live, live_cap, d_n_live, 1, d_out, out_stride, out_capacity, d_out_certs,
+                      d_out_status, &sl, stream);
 }
 
 int ramcrc_recovery_partition_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,

@@ -25,6 +25,7 @@
 #include "murmur3.h"
 #include "partition_rules.h"
 #include "resolve_rules.h"
+#include "sidelog_rules.h"
 
 namespace {
 
@@ -226,13 +227,19 @@ int ramcrc_segment_fill_objects(uint8_t* seg, uint32_t capacity, uint32_t value_
 // Segment::append (src/Segment.cc:197-228) per placement, into the recovery
 // segment (source segment, partition), while hasSpaceFor (:136-154) holds.
 // Two passes over the list: the first checks it, so a refused call writes
-// nothing.
-int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
-                                const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
-                                uint64_t n_entries, const ramcrc_placement* place, uint64_t n_place,
-                                uint32_t n_part, void* out, uint64_t out_stride,
-                                uint32_t out_capacity, ramcrc_seg_cert* out_certs,
-                                ramcrc_append_status* out_status)
+// nothing.  pdst (nullable, one per placement): the offset of the placement's
+// entry header in its output, or 0xFFFFFFFF when it was not appended, as the
+// device keeps it (AppDesc::pdst) -- what the side log builds on.
+}  // extern "C"
+
+namespace {
+constexpr uint32_t kNotAppended = 0xFFFFFFFFu;
+
+int append_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                uint64_t n_entries, const ramcrc_placement* place, uint64_t n_place,
+                uint32_t n_part, void* out, uint64_t out_stride, uint32_t out_capacity,
+                ramcrc_seg_cert* out_certs, ramcrc_append_status* out_status, uint32_t* pdst)
 {
     if (n_part == 0 || out_stride < out_capacity || n_seg > 0xFFFFFFFFull)
         return RAMCRC_EINVAL;
@@ -282,6 +289,8 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
     for (uint64_t i = 0; i < n_place; i++) {
         const ramcrc_seg_entry& r = entries[place[i].record];
         const uint64_t k = uint64_t(r.segment) * n_part + place[i].partition;
+        if (pdst)
+            pdst[i] = kNotAppended;
         if (out_status[k].flags != RAMCRC_SEG_OK)
             continue;   // bad source, or full: nothing more is appended
         const uint32_t len = r.length;
@@ -301,6 +310,8 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
         memcpy(e + 1 + lb, static_cast<const uint8_t*>(base) + r.segment * seg_stride + src, len);
         out_certs[k].segment_length = head + 1 + lb + len;
         out_status[k].entries++;
+        if (pdst)
+            pdst[i] = head;
     }
     for (uint64_t k = 0; k < n_out; k++) {
         uint8_t lenle[4];
@@ -308,6 +319,91 @@ int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t 
             lenle[b] = uint8_t(out_certs[k].segment_length >> (8 * b));
         out_certs[k].checksum = ~ramcrc_update(out_certs[k].checksum, lenle, 4);
     }
+    return RAMCRC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ramcrc_recovery_append_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                                const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                                uint64_t n_entries, const ramcrc_placement* place, uint64_t n_place,
+                                uint32_t n_part, void* out, uint64_t out_stride,
+                                uint32_t out_capacity, ramcrc_seg_cert* out_certs,
+                                ramcrc_append_status* out_status)
+{
+    return append_host(base, seg_stride, n_seg, status, entries, n_entries, place, n_place, n_part,
+                       out, out_stride, out_capacity, out_certs, out_status, nullptr);
+}
+
+// ObjectManager::replaySegment's sideLog->append of every kept record
+// (src/ObjectManager.cc:720-734, :840-867): the append at one partition, then
+// one pass over the list that rewrites the appended tombstones in the output
+// (:845-851), notes the references and counts (sidelog_rules.h).
+int ramcrc_replay_sidelog_host(const void* base, uint64_t seg_stride, uint64_t n_seg,
+                               const ramcrc_seg_status* status, const ramcrc_seg_entry* entries,
+                               uint64_t n_entries, const ramcrc_placement* live, uint64_t n_live,
+                               uint32_t timestamp, void* out, uint64_t out_stride,
+                               uint32_t out_capacity, ramcrc_seg_cert* out_certs,
+                               ramcrc_append_status* out_status, ramcrc_log_ref* refs,
+                               ramcrc_sidelog_counts* counts)
+{
+    if (!counts || n_live > 0xFFFFFFFFull)
+        return RAMCRC_EINVAL;
+    if (n_seg == 0)
+        return out_stride < out_capacity ? RAMCRC_EINVAL : RAMCRC_OK;
+    std::vector<uint32_t> pdst;
+    try {
+        pdst.resize(n_live);
+    } catch (const std::bad_alloc&) {
+        return RAMCRC_ENOMEM;
+    }
+    const int rc = append_host(base, seg_stride, n_seg, status, entries, n_entries, live, n_live, 1,
+                               out, out_stride, out_capacity, out_certs, out_status, pdst.data());
+    if (rc)
+        return rc;
+    ramcrc_sidelog_counts c{};
+    for (uint64_t i = 0; i < n_live; i++) {
+        const ramcrc_seg_entry& r = entries[live[i].record];
+        const bool app = pdst[i] != kNotAppended;
+        if (refs)
+            refs[i] = app ? ramcrc_log_ref{r.segment, pdst[i]}
+                          : ramcrc_log_ref{RAMCRC_LOG_REF_NONE, RAMCRC_LOG_REF_NONE};
+        if (!app) {
+            c.left_out++;
+            continue;
+        }
+        const uint32_t len = r.length;
+        switch (ramcrc_sl::kind(r.header & 0x3f, len)) {
+        case ramcrc_sl::kObject:
+            c.objects++;
+            c.object_bytes += len;
+            break;
+        case ramcrc_sl::kShortTombstone:
+            c.short_tombstones++;
+            break;
+        case ramcrc_sl::kOther:
+            c.other++;
+            break;
+        case ramcrc_sl::kTombstone: {
+            c.tombstones++;
+            c.tombstone_bytes += len;
+            const uint32_t lb = len < 0x100u ? 1 : len < 0x10000u ? 2 : len < 0x1000000u ? 3 : 4;
+            uint8_t* t = static_cast<uint8_t*>(out) + r.segment * out_stride + pdst[i] + 1 + lb;
+            for (uint32_t b = 0; b < ramcrc_sl::kChecksumAt; b++) {
+                uint32_t v;
+                if (ramcrc_sl::stamped(b, timestamp, v))
+                    t[b] = uint8_t(v);
+            }
+            uint32_t ck = ramcrc_update(0xFFFFFFFFu, t, ramcrc_sl::kChecksumAt);
+            ck = ~ramcrc_update(ck, t + ramcrc_sl::kTombHeaderBytes, len - ramcrc_sl::kTombHeaderBytes);
+            for (int b = 0; b < 4; b++)
+                t[ramcrc_sl::kChecksumAt + b] = uint8_t(ck >> (8 * b));
+            break;
+        }
+        }
+    }
+    *counts = c;
     return RAMCRC_OK;
 }
 

@@ -92,6 +92,10 @@ def lib():
                                                 vp, u64, u32, vp, vp, vp]),
         "ramcrc_recovery_append_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u64, u32, vp, u64, u32,
                                               vp, vp]),
+        "ramcrc_replay_sidelog_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u64, vp, u32,
+                                               vp, u64, u32, vp, vp, vp, vp, vp]),
+        "ramcrc_replay_sidelog_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u64, u32, vp, u64, u32,
+                                             vp, vp, vp, vp]),
         "ramcrc_recovery_partition_device": (i32, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u32, u32,
                                                    vp, u64, vp, vp, vp, vp]),
         "ramcrc_recovery_partition_host": (i32, [vp, u64, u64, vp, vp, u64, vp, u32, u32, vp, u64,
@@ -278,6 +282,44 @@ def recovery_append_host(segments, seg_stride, n_seg, status, entries, place, n_
                                            p(out), out_stride, out_capacity, p(certs), p(ostat))
     _check(rc, "ramcrc_recovery_append_host")
     return certs, ostat
+
+
+def replay_sidelog_host(segments, seg_stride, n_seg, status, entries, live, timestamp, out,
+                        out_stride, out_capacity, want_refs=True):
+    """ObjectManager::replaySegment's side log on the host
+    (ramcrc_replay_sidelog_host): the append at one partition with kept
+    tombstones rewritten (segmentId 0, `timestamp`, a recomputed checksum).
+    Arrays as recovery_append_host takes them; live uint32 [m, 2] (record, 0).
+    Returns (certs uint32 [n_seg, 2], status uint32 [n_seg, 2], refs uint32
+    [m, 2] (output, offset; LOG_REF_NONE twice where not appended) or None,
+    counts: a segments.SIDELOG_COUNTS_DTYPE scalar); raises RamcrcError (code
+    EINVAL) where the device form refuses."""
+    from . import segments as _seg
+
+    def arr(a, dtype):
+        a = np.asarray(a)
+        if a.dtype.fields is not None:
+            a = a.view(np.uint32)
+        if a.dtype != dtype or not a.flags.c_contiguous:
+            raise RamcrcError(f"expected a contiguous {np.dtype(dtype).name} array")
+        return a
+    segments, out = arr(segments, np.uint8), arr(out, np.uint8)
+    status, entries, live = arr(status, np.uint32), arr(entries, np.uint32), arr(live, np.uint32)
+    if (segments.size < n_seg * seg_stride or out.size < n_seg * out_stride
+            or status.size < 4 * n_seg or not out.flags.writeable):
+        raise RamcrcError("replay_sidelog_host: an array is smaller than its geometry")
+    m = live.size // 2
+    certs = np.zeros((n_seg, 2), np.uint32)
+    ostat = np.zeros((n_seg, 2), np.uint32)
+    refs = np.zeros((m, 2), np.uint32) if want_refs else None
+    counts = np.zeros(1, _seg.SIDELOG_COUNTS_DTYPE)
+    p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None else None
+    rc = lib().ramcrc_replay_sidelog_host(p(segments), seg_stride, n_seg, p(status), p(entries),
+                                          entries.size // 4, p(live), m, int(timestamp), p(out),
+                                          out_stride, out_capacity, p(certs), p(ostat), p(refs),
+                                          p(counts))
+    _check(rc, "ramcrc_replay_sidelog_host")
+    return certs, ostat, refs, counts[0]
 
 
 def recovery_partition_host(segments, seg_stride, n_seg, status, entries, tablets, n_part,
@@ -621,6 +663,29 @@ class Context:
             _ptr(n_entries), _ptr(place), pcap, _ptr(n_place), n_part, _ptr(out), out_stride,
             out_capacity, _ptr(out_certs), _ptr(out_status), _stream(stream))
         _check(rc, "ramcrc_recovery_append_device")
+        return out_certs
+
+    def replay_sidelog(self, data, seg_stride, nseg, status, entries, n_entries, live, n_live,
+                       timestamp, out, out_stride, out_capacity, out_certs, out_status, counts,
+                       refs=None, stream=None):
+        """The side log of a replay (ramcrc_replay_sidelog_device): the append
+        at one partition over a live list (replay_resolve's or
+        ReplayTable.live's), kept tombstones rewritten with segmentId 0,
+        `timestamp` and a recomputed checksum.  Tensors as recovery_append
+        takes them; counts: int64 CUDA [7] out (segments.SIDELOG_COUNTS_DTYPE);
+        refs: int32 CUDA [cap, 2] out (output, offset) or None.  timestamp is
+        passed by value: a captured graph replays the captured one.
+        Asynchronous; a refused list shows in check()."""
+        ecap = 0 if entries is None else entries.shape[0]
+        lcap = 0 if live is None else live.shape[0]
+        if refs is not None and refs.shape[0] < lcap:
+            raise RamcrcError("replay_sidelog: fewer refs than the live list holds")
+        rc = lib().ramcrc_replay_sidelog_device(
+            self._h, _ptr(data), seg_stride, nseg, _ptr(status), _ptr(entries), ecap,
+            _ptr(n_entries), _ptr(live), lcap, _ptr(n_live), int(timestamp), _ptr(out), out_stride,
+            out_capacity, _ptr(out_certs), _ptr(out_status), _ptr(refs), _ptr(counts),
+            _stream(stream))
+        _check(rc, "ramcrc_replay_sidelog_device")
         return out_certs
 
     def recovery_partition(self, data, seg_stride, nseg, status, entries, n_entries, tablets,

@@ -53,6 +53,13 @@ REPLAY_TABLE_STATS_DTYPE = np.dtype([("keys", "<u8"), ("live_objects", "<u8"),
                                      ("live_tombstones", "<u8"), ("safe_version", "<u8"),
                                      ("batches", "<u8"), ("spoiled", "<u8")])
 REPLAY_TABLE_MAX_BATCHES = 65536
+# ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
+# (ramcrc_replay_sidelog_device / _host)
+LOG_REF_DTYPE = np.dtype([("segment", "<u4"), ("offset", "<u4")])
+SIDELOG_COUNTS_DTYPE = np.dtype([("objects", "<u8"), ("tombstones", "<u8"), ("other", "<u8"),
+                                 ("object_bytes", "<u8"), ("tombstone_bytes", "<u8"),
+                                 ("short_tombstones", "<u8"), ("left_out", "<u8")])
+LOG_REF_NONE = 0xFFFFFFFF
 LOG_ENTRY_TYPE_SEGHEADER = 1    # src/LogEntryTypes.h:32
 LOG_ENTRY_TYPE_RPCRESULT = 7    # src/LogEntryTypes.h:50
 LOG_ENTRY_TYPE_OBJ = 2          # src/LogEntryTypes.h:35
