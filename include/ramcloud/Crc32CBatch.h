@@ -391,6 +391,22 @@ class ReplayTable {
               "ramcrc_replay_table_stats_device");
     }
 
+    /// What the table holds for each of nQueries keys as it stands now, the
+    /// batched ObjectManager::lookup / readObject of MasterService::multiRead
+    /// (src/MasterService.cc:1352-1415): per key the winner's {batch, record},
+    /// version and kind, and for an object where its value lies in that
+    /// batch's segments.  d_keyHash and d_counts are nullable.  Read-only on
+    /// the table.
+    void
+    lookup(const void* d_keys, uint64_t keysBytes, const ramcrc_lookup_key* d_queries,
+           uint64_t nQueries, const uint64_t* d_keyHash, ramcrc_lookup_result* d_results,
+           ramcrc_lookup_counts* d_counts, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_lookup_device(table, d_keys, keysBytes, d_queries, nQueries,
+                                                d_keyHash, d_results, d_counts, stream),
+              "ramcrc_replay_table_lookup_device");
+    }
+
   private:
     static void
     check(int rc, const char* what)

@@ -598,9 +598,10 @@ int ramcrc_replay_resolve_host(const void* base, uint64_t seg_stride, uint64_t n
  *
  * Not done, as in the one-call: the synthesized tombstone for an overwritten
  * object (:697-717, :804-835), raiseSafeVersion(version + 1) (:797), PREP and
- * the other transaction records, and insertion into the master's own table.
- * The rewrite of a kept tombstone's header is ramcrc_replay_sidelog_device's,
- * below.
+ * the other transaction records, and insertion into the master's own table:
+ * the table is one of its own, asked by batch with live and by key with
+ * ramcrc_replay_table_lookup_device, below.  The rewrite of a kept
+ * tombstone's header is ramcrc_replay_sidelog_device's, below.
  *
  * Concurrency.  All calls are stream-ordered and asynchronous; calls on one
  * table are serialised by the handle; a caller who uses several streams
@@ -684,6 +685,102 @@ int ramcrc_replay_table_live_host(ramcrc_replay_table_host* t, uint32_t batch,
                                   uint64_t live_cap, uint64_t* n_live,
                                   ramcrc_resolve_counts* counts);
 int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_table_stats* stats);
+
+/* What the table holds for a key: the batched form of ObjectManager::lookup
+ * (src/ObjectManager.cc:2704-2741) and readObject (:325-369) as
+ * MasterService::multiRead runs them per key (src/MasterService.cc:1352-1415),
+ * against the replay table.  The live query answers by batch and record; this
+ * call answers by key.  It reads the table and writes only its outputs.
+ *
+ * Answer.  Query q's answer is the winner, as the table stands now -- after
+ * every add enqueued before the call on the stream and before any enqueued
+ * after it --, of the key {table_id, key_len, the key_len bytes at d_keys +
+ * key_off}.  Key identity is the table's: all 64 bits of the table id, the
+ * length, the bytes; a hash only narrows the search.  The defining property:
+ * for every participant record i of every added batch, the lookup of i's own
+ * key returns as `ref` exactly what ramcrc_replay_table_live_device writes to
+ * d_winner[i] for that batch at the same moment.  A key no participant
+ * carries is RAMCRC_LOOKUP_ABSENT.
+ *
+ * Hashes.  d_key_hash[q], where given, must be the same function of (table
+ * id, key) that the adds used; NULL means Key::getHash, computed in the call.
+ *
+ * Version and kind.  `version` is the winner's (OBJ: u64 at payload 8,
+ * OBJTOMB: at 16); `kind` says which of the two it is.  A tombstone is what
+ * readObject answers with STATUS_OBJECT_DOESNT_EXIST (:341); RejectRules are
+ * the caller's, applied to the returned version.
+ *
+ * Value location (OBJECT only), after Object::getValueOffset / getValueLength
+ * (src/Object.cc:647-676).  With nk = u8 at payload 24 the value begins at
+ * payload offset 25 + 2 * nk + cum[nk - 1] (25 when nk = 0), cum[nk - 1] the
+ * last u16 of the cumulative key length array.  value_off is that offset plus
+ * the payload's offset in its segment, `segment` the winner's segment number
+ * within its batch, value_len the rest of the payload: the value is the
+ * value_len bytes at that batch's d_base + segment * seg_stride + value_off.
+ * If the key table or the keys run past the payload -- only a multi-key
+ * object can, since a participant's first key was checked -- value_len = 0
+ * and value_off is the payload's end (the reference's getValueLength() == 0
+ * when fillKeyOffsets fails).  Nothing outside the record's payload is read.
+ *
+ * Bad queries.  A query is RAMCRC_LOOKUP_BAD_KEY when key_len > 65,535,
+ * reserved != 0, or key_off + key_len > keys_bytes (the sum in 64 bits,
+ * overflow included).  Its ref is none and every other field is as for
+ * ABSENT; no byte of the key buffer or the table is read for it; it neither
+ * refuses the call nor sets the context's sticky bit.  Queries may repeat:
+ * every copy gets the same answer.
+ *
+ * d_counts (nullable) receives how many queries got each kind; spoiled is 0.
+ * On a spoiled table d_results stays untouched, *d_counts becomes {0, 0, 0,
+ * 0, 1} and no new refusal is raised: the rule of live and stats.
+ *
+ * n_queries = 0 is legal (zeroed counts, nothing else); n_queries < 2^32 - 1;
+ * d_queries 8-byte aligned, d_results 16-byte aligned, d_keys free.  Key
+ * bytes are fetched as the aligned 16-byte words that hold at least one byte
+ * of a usable query's key.  No table word, descriptor, work array or batch
+ * counter is written: a lookup between two adds changes no later answer.
+ * Lifetime and concurrency are the table's; the key buffer, queries and
+ * hashes belong to the caller again once the stream has passed the call.
+ * The counters use one 128-byte line of the context's scratch: after
+ * ramcrc_ctx_reserve(ctx, 32, 0), or after any earlier call on the context
+ * that reserved as much, a lookup does not allocate. */
+typedef struct ramcrc_lookup_key {
+    uint64_t table_id;   /* all 64 bits compared */
+    uint64_t key_off;    /* byte offset of the key in the caller's key buffer */
+    uint32_t key_len;    /* 0 .. 65,535 (KeyLength is 16 bits); the empty key is a key */
+    uint32_t reserved;   /* must be 0 */
+} ramcrc_lookup_key;     /* 24 bytes */
+
+#define RAMCRC_LOOKUP_ABSENT    0u   /* no record of this key was ever added */
+#define RAMCRC_LOOKUP_OBJECT    1u
+#define RAMCRC_LOOKUP_TOMBSTONE 2u   /* readObject: STATUS_OBJECT_DOESNT_EXIST (:341) */
+#define RAMCRC_LOOKUP_BAD_KEY   3u   /* the query itself is unusable; nothing was read for it */
+
+typedef struct ramcrc_lookup_result {
+    ramcrc_replay_ref ref;   /* the key's winner, {batch, record}; none = {0xFFFFFFFF, 0xFFFFFFFF} */
+    uint64_t version;        /* the winner's version; 0 when there is none */
+    uint32_t kind;           /* RAMCRC_LOOKUP_* */
+    uint32_t segment;        /* OBJECT: the winner's segment number within its batch; else 0xFFFFFFFF */
+    uint32_t value_off;      /* OBJECT: offset of the value from the start of that segment; else 0 */
+    uint32_t value_len;      /* OBJECT: Object::getValueLength(); else 0 */
+} ramcrc_lookup_result;      /* 32 bytes */
+
+typedef struct ramcrc_lookup_counts {
+    uint64_t objects, tombstones, absent, bad, spoiled;
+} ramcrc_lookup_counts;
+
+int ramcrc_replay_table_lookup_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                      const ramcrc_lookup_key* d_queries, uint64_t n_queries,
+                                      const uint64_t* d_key_hash /* nullable */,
+                                      ramcrc_lookup_result* d_results,
+                                      ramcrc_lookup_counts* d_counts /* nullable */, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same answers.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_lookup_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* queries, uint64_t n_queries,
+                                    const uint64_t* key_hash, ramcrc_lookup_result* results,
+                                    ramcrc_lookup_counts* counts);
 
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,

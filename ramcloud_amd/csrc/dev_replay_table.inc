@@ -1,6 +1,7 @@
 // The persistent replay table (ramcrc_replay_table_*): k_rtab_zero,
 // k_rtab_open, k_rtab_insert, k_rtab_pick (an add), k_rtab_tiles, k_rtab_scan,
-// k_rtab_emit (a live query), k_rtab_stats (DESIGN.md 5.11).
+// k_rtab_emit (a live query), k_rtab_stats (DESIGN.md 5.11), k_rtab_lookup
+// (a lookup by key, DESIGN.md 5.13).
 // Part of ramcrc_device.hip (one translation unit: the kernels share the
 // g_tab tables, LDS layouts and templates without relocatable device code).
 // Included only from there, after dev_resolve.inc; not a standalone header.
@@ -457,6 +458,156 @@ __global__ __launch_bounds__(kPartThreads) void k_rtab_stats(RtabDesc a)
             if (nk - no)
                 atomicAdd(reinterpret_cast<unsigned long long*>(&st->live_tombstones), nk - no);
         }
+    }
+}
+
+// ----------------------------------------------------------- k_rtab_lookup
+// What the table holds for a key (ramcrc_replay_table_lookup_device, DESIGN.md
+// 5.13): k_rtab_insert's probe with the writes taken out.  One query per lane
+// in tiles of kPartThreads; from hash & mask the lane steps to the first slot
+// whose claim is 0 (absent: the table never deletes) or whose claimant's key,
+// read through its batch's descriptor, equals the query's; there the pick
+// names the winner, whose record -- not necessarily the claimant's -- gives
+// the version and the value's place.  Every table word lies behind a kernel
+// boundary and is read plainly; nothing of the table is written.  A query is
+// a chain of dependent loads (query, claim, descriptor, record, key, pick,
+// winner's record, its key table): residency hides it, so the kernel keeps no
+// LDS in the loop and few registers.
+// The counters: every lane counts its kinds in registers; at the end one
+// reduction per workgroup (wave shuffles, then LDS), one atomic per nonzero
+// counter on the scratch line, and the last workgroup to finish copies the
+// line out, as k_sl_stamp does.
+constexpr uint32_t kLookCountWords = 32;   // scratch: one 128-byte line of counters
+constexpr int kLookCounters = 4;           // objects, tombstones, absent, bad; spoiled is written as 0
+constexpr int kLookTicket = 8;             // counts[kLookTicket]: workgroups that have finished
+static_assert(sizeof(ramcrc_lookup_key) == 24 && sizeof(ramcrc_lookup_result) == 32, "lookup ABI");
+static_assert(sizeof(ramcrc_lookup_counts) == (kLookCounters + 1) * sizeof(uint64_t), "lookup counters");
+static_assert((kLookTicket + 1) * sizeof(uint64_t) <= kLookCountWords * sizeof(uint32_t), "counter line");
+
+struct LookDesc {
+    uint64_t keys;                      // the caller's key buffer
+    uint64_t keys_bytes;
+    const uint64_t* queries;            // three words each: table id, key_off, reserved << 32 | key_len
+    uint64_t nq;
+    const uint64_t* key_hash;           // nullable: the caller's hashes
+    u32x4* results;                     // two each
+    ramcrc_lookup_counts* counts_out;   // nullable
+    unsigned long long* counts;         // scratch line, zeroed by the call: counters, ticket
+};
+
+// ramcrc_lookup_counts' field of a kind.
+__device__ __forceinline__ int look_counter(uint32_t kind)
+{
+    return kind == RAMCRC_LOOKUP_OBJECT ? 0 : kind == RAMCRC_LOOKUP_TOMBSTONE ? 1
+           : kind == RAMCRC_LOOKUP_ABSENT ? 2 : 3;
+}
+
+template <bool kGiven>
+__global__ __launch_bounds__(kPartThreads) void k_rtab_lookup(RtabDesc a, LookDesc q)
+{
+    __shared__ unsigned long long wsum[kLookCounters * (kPartThreads / kWaveSize)];
+    __shared__ uint32_t is_last;
+    if (rtab_refused(a)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && q.counts_out)
+            *q.counts_out = ramcrc_lookup_counts{0, 0, 0, 0, 1};
+        return;
+    }
+    const uint64_t mask = a.nslots - 1;
+    uint32_t cnt[kLookCounters] = {};   // (a lane takes fewer than 2^32 queries)
+    for (uint64_t i0 = uint64_t(blockIdx.x) * kPartThreads; i0 < q.nq;
+         i0 += uint64_t(gridDim.x) * kPartThreads) {
+        const uint64_t i = i0 + threadIdx.x;
+        if (i >= q.nq)
+            continue;
+        const uint64_t table_id = q.queries[3 * i], off = q.queries[3 * i + 1];
+        const uint64_t lr = q.queries[3 * i + 2];
+        const uint32_t len = uint32_t(lr);
+        ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
+        if (!ramcrc_look::bad_query(off, len, uint32_t(lr >> 32), q.keys_bytes)) {
+            res.kind = RAMCRC_LOOKUP_ABSENT;
+            const uint64_t addr = q.keys + off;
+            uint64_t hash;
+            if constexpr (kGiven)
+                hash = q.key_hash[i];
+            else
+                hash = part_key_hash(table_id, addr, len);
+            // bounded by the slot count, as the insert's probe is
+            uint64_t s = hash & mask;
+            for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+                const uint64_t c = *rtab_word(a, s, 2);
+                if (c == 0)
+                    break;
+                const ResKey k = rtab_key_of(a.batches[c >> 32], (c & 0xFFFFFFFFull) - 1);
+                if (k.table_id != table_id || k.len != len || !res_bytes_equal(k.addr, addr, len))
+                    continue;
+                const uint64_t pick = *rtab_word(a, s, 1);
+                if (pick == 0)   // (between adds every claimed slot has one)
+                    break;
+                const uint64_t rank = ~pick;   // as rtab_winner decodes it
+                const uint32_t wb = uint32_t(rank >> 32) & 0xFFFFu, wr = uint32_t(rank);
+                const RtabBatch& b = a.batches[wb];
+                const u32x4 r = b.entries[wr];
+                const uint32_t pay = r.y + 1 + ((r.w >> 6) & 3) + 1;
+                const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
+                res.ref = ramcrc_replay_ref{wb, wr};
+                res.version = ramcrc_res::version(r.w & 0x3f, rd);
+                if ((rank >> 48) & 1) {
+                    const ramcrc_look::Value v = ramcrc_look::object_value(r.z, rd);
+                    res.kind = RAMCRC_LOOKUP_OBJECT;
+                    res.segment = r.x;
+                    res.value_off = pay + v.off;
+                    res.value_len = v.len;
+                } else {
+                    res.kind = RAMCRC_LOOKUP_TOMBSTONE;
+                }
+                break;
+            }
+        }
+        u32x4 lo, hi;
+        lo.x = res.ref.batch;
+        lo.y = res.ref.record;
+        lo.z = uint32_t(res.version);
+        lo.w = uint32_t(res.version >> 32);
+        hi.x = res.kind;
+        hi.y = res.segment;
+        hi.z = res.value_off;
+        hi.w = res.value_len;
+        q.results[2 * i] = lo;
+        q.results[2 * i + 1] = hi;
+#pragma unroll
+        for (int k = 0; k < kLookCounters; k++)
+            cnt[k] += look_counter(res.kind) == k;
+    }
+    if (!q.counts_out)
+        return;
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kLookCounters; k++) {
+        unsigned long long v = cnt[k];
+#pragma unroll
+        for (int d = 1; d < kWaveSize; d <<= 1)
+            v += __shfl_xor(v, d);
+        if ((t & (kWaveSize - 1)) == 0)
+            wsum[k * (kPartThreads / kWaveSize) + t / kWaveSize] = v;
+    }
+    __syncthreads();
+    if (t < kLookCounters) {
+        unsigned long long v = 0;
+        for (int w = 0; w < kPartThreads / kWaveSize; w++)
+            v += wsum[t * (kPartThreads / kWaveSize) + w];
+        if (v)
+            atomicAdd(&q.counts[t], v);
+    }
+    __syncthreads();   // this workgroup has issued its sums
+    if (t == 0) {
+        __threadfence();
+        is_last = atomicAdd(&q.counts[kLookTicket], 1ull) + 1 == gridDim.x;
+    }
+    __syncthreads();
+    if (is_last && t <= kLookCounters) {
+        __threadfence();
+        reinterpret_cast<unsigned long long*>(q.counts_out)[t] =
+            t < kLookCounters ? atomicAdd(&q.counts[t], 0ull) : 0ull;   // spoiled: 0
     }
 }
 

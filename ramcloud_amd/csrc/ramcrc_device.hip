@@ -61,7 +61,8 @@
 //   dev_sidelog.inc  k_sl_stamp (rewritten tombstones, references, counts)
 //   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
 //   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
-//   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table)
+//   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table,
+//                         and its lookup by key)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -79,6 +80,7 @@
 #include "walk_rules.h"
 #include "murmur3.h"
 #include "partition_rules.h"
+#include "lookup_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "ramcrc.h"
@@ -1430,6 +1432,52 @@ int ramcrc_replay_table_stats_device(ramcrc_replay_table* t, ramcrc_replay_table
     HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(*d_stats), s));
     hipLaunchKernelGGL(k_rtab_stats, dim3(rtab_grid(c, t->nslots, kPartThreads)), dim3(kPartThreads),
                        0, s, a);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_lookup_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                      const ramcrc_lookup_key* d_queries, uint64_t n_queries,
+                                      const uint64_t* d_key_hash, ramcrc_lookup_result* d_results,
+                                      ramcrc_lookup_counts* d_counts, void* stream)
+{
+    if (!t || n_queries >= 0xFFFFFFFFull || (n_queries && (!d_queries || !d_results)) ||
+        (keys_bytes && !d_keys))
+        return RAMCRC_EINVAL;
+    const uint64_t K = reinterpret_cast<uint64_t>(d_keys);
+    if ((reinterpret_cast<uint64_t>(d_queries) & 7) || (reinterpret_cast<uint64_t>(d_results) & 15) ||
+        K > UINT64_MAX - keys_bytes)
+        return RAMCRC_EINVAL;
+    if (n_queries == 0 && !d_counts)
+        return RAMCRC_OK;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // the counters: the first line of the chunk-partial buffer (ramcrc.h
+    // states this size)
+    int rc = reserve_locked(c, kLookCountWords, 0);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    LookDesc q{};
+    q.keys = K;
+    q.keys_bytes = keys_bytes;
+    q.queries = reinterpret_cast<const uint64_t*>(d_queries);
+    q.nq = n_queries;
+    q.key_hash = d_key_hash;
+    q.results = reinterpret_cast<u32x4*>(d_results);
+    q.counts_out = d_counts;
+    q.counts = reinterpret_cast<unsigned long long*>(c->partials);
+    if (d_counts)
+        HIPCHK(hipMemsetAsync(q.counts, 0, kLookCountWords * sizeof(uint32_t), s));
+    // (at least one workgroup: an empty call still gets its counts)
+    const dim3 grid(rtab_grid(c, n_queries, kPartThreads));
+    if (d_key_hash)
+        hipLaunchKernelGGL(k_rtab_lookup<true>, grid, dim3(kPartThreads), 0, s, a, q);
+    else
+        hipLaunchKernelGGL(k_rtab_lookup<false>, grid, dim3(kPartThreads), 0, s, a, q);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }

@@ -24,6 +24,7 @@
 #include "gf2.h"
 #include "murmur3.h"
 #include "partition_rules.h"
+#include "lookup_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 
@@ -685,6 +686,9 @@ struct ramcrc_replay_table_host {
         const uint64_t* work;
         uint64_t n;
         uint64_t objects, tombstones, malformed;
+        const uint8_t* base;   // the batch's segments and record table: a lookup reads its winner's record
+        uint64_t stride;
+        const ramcrc_seg_entry* entries;
     };
     uint64_t key_cap = 0, keys = 0, safe_version = 0;
     uint32_t max_batches = 0;
@@ -752,7 +756,8 @@ int ramcrc_replay_table_add_host(ramcrc_replay_table_host* t, const void* base, 
         return RAMCRC_EINVAL;
     const uint64_t bno = t->batches.size();
     try {
-        t->batches.push_back(ramcrc_replay_table_host::Batch{work, n_entries, 0, 0, 0});
+        t->batches.push_back(ramcrc_replay_table_host::Batch{
+            work, n_entries, 0, 0, 0, static_cast<const uint8_t*>(base), seg_stride, entries});
     } catch (...) {
         return RAMCRC_ENOMEM;
     }
@@ -890,6 +895,79 @@ int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_ta
     }
     stats->safe_version = t->safe_version;
     stats->batches = t->batches.size();
+    return RAMCRC_OK;
+}
+
+// What the table holds for a key (the rules of lookup_rules.h): the add's
+// probe without the writes, then the winner's record for the version and the
+// value's place.
+int ramcrc_replay_table_lookup_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* queries, uint64_t n_queries,
+                                    const uint64_t* key_hash, ramcrc_lookup_result* results,
+                                    ramcrc_lookup_counts* counts)
+{
+    namespace rl = ramcrc_look;
+    if (!t || n_queries >= 0xFFFFFFFFull || (n_queries && (!queries || !results)) ||
+        (keys_bytes && !keys))
+        return RAMCRC_EINVAL;
+    if (t->spoiled) {
+        if (counts)
+            *counts = ramcrc_lookup_counts{0, 0, 0, 0, 1};
+        return RAMCRC_OK;
+    }
+    struct Rd {
+        const uint8_t* pay;
+        uint32_t u8(uint32_t o) const { return pay[o]; }
+        uint32_t u16(uint32_t o) const { return ld16(pay + o); }
+        uint32_t u32(uint32_t o) const { return ld32(pay + o); }
+        uint64_t u64(uint32_t o) const { return ld64(pay + o); }
+    };
+    ramcrc_lookup_counts ct{0, 0, 0, 0, 0};
+    const uint8_t* const kb = static_cast<const uint8_t*>(keys);
+    const uint64_t mask = t->slots.size() - 1;
+    for (uint64_t i = 0; i < n_queries; i++) {
+        ramcrc_lookup_key q;   // (no alignment rule)
+        memcpy(&q, reinterpret_cast<const uint8_t*>(queries) + i * sizeof(q), sizeof(q));
+        ramcrc_lookup_result res = rl::no_result(RAMCRC_LOOKUP_BAD_KEY);
+        if (rl::bad_query(q.key_off, q.key_len, q.reserved, keys_bytes)) {
+            ct.bad++;
+        } else {
+            res.kind = RAMCRC_LOOKUP_ABSENT;
+            const uint8_t* const key = q.key_len ? kb + q.key_off : nullptr;
+            const uint64_t hash = key_hash ? key_hash[i] : ramcrc::key_hash(q.table_id, key, q.key_len);
+            uint64_t s = hash & mask;
+            for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+                const ramcrc_replay_table_host::Slot& sl = t->slots[s];
+                if (!sl.claim)
+                    break;
+                if (sl.table_id != q.table_id || sl.key_len != q.key_len ||
+                    (q.key_len && memcmp(sl.key, key, q.key_len)))
+                    continue;
+                const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
+                const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
+                const ramcrc_seg_entry& r = bt.entries[wr];
+                const uint32_t pay = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+                res.ref = ramcrc_replay_ref{wb, wr};
+                res.version = sl.version;
+                if ((sl.rank >> 48) & 1) {
+                    const rl::Value v =
+                        rl::object_value(r.length, Rd{bt.base + r.segment * bt.stride + pay});
+                    res.kind = RAMCRC_LOOKUP_OBJECT;
+                    res.segment = r.segment;
+                    res.value_off = pay + v.off;
+                    res.value_len = v.len;
+                } else {
+                    res.kind = RAMCRC_LOOKUP_TOMBSTONE;
+                }
+                break;
+            }
+            (res.kind == RAMCRC_LOOKUP_OBJECT ? ct.objects
+             : res.kind == RAMCRC_LOOKUP_TOMBSTONE ? ct.tombstones : ct.absent)++;
+        }
+        memcpy(reinterpret_cast<uint8_t*>(results) + i * sizeof(res), &res, sizeof(res));
+    }
+    if (counts)
+        *counts = ct;
     return RAMCRC_OK;
 }
 

@@ -118,6 +118,8 @@ def lib():
                                                _c.POINTER(u32)]),
         "ramcrc_replay_table_live_host": (i32, [vp, u32, vp, vp, u64, _c.POINTER(u64), vp]),
         "ramcrc_replay_table_stats_host": (i32, [vp, vp]),
+        "ramcrc_replay_table_lookup_device": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "ramcrc_replay_table_lookup_host": (i32, [vp, vp, u64, vp, u64, vp, vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -474,6 +476,29 @@ class ReplayTableHost:
         _check(lib().ramcrc_replay_table_stats_host(self._h, _c.c_void_p(st.ctypes.data)),
                "ramcrc_replay_table_stats_host")
         return st[0]
+
+    def lookup(self, keys, queries, key_hash=None):
+        """What the table holds for each key.  keys: uint8 [keys_bytes], the
+        key buffer; queries: segments.LOOKUP_KEY_DTYPE [n]
+        (segments.lookup_queries packs both); key_hash: uint64 [n] or None
+        (computed).  Returns (results: segments.LOOKUP_RESULT_DTYPE [n], counts:
+        a segments.LOOKUP_COUNTS_DTYPE scalar); on a spoiled table the results
+        are the wrapper's zeros and counts["spoiled"] is 1."""
+        from . import segments as _seg
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        queries = np.ascontiguousarray(queries, _seg.LOOKUP_KEY_DTYPE).reshape(-1)
+        n = queries.shape[0]
+        if key_hash is not None:
+            key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+            if key_hash.size < n:
+                raise RamcrcError("ReplayTableHost.lookup: fewer hashes than queries")
+        results = np.zeros(n, _seg.LOOKUP_RESULT_DTYPE)
+        counts = np.zeros(1, _seg.LOOKUP_COUNTS_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_lookup_host(self._h, p(keys), keys.size, p(queries), n,
+                                                   p(key_hash), p(results), p(counts))
+        _check(rc, "ramcrc_replay_table_lookup_host")
+        return results, counts[0]
 
 
 # ---------------------------------------------------------------- device
@@ -884,6 +909,30 @@ class ReplayTable:
         _check(lib().ramcrc_replay_table_stats_device(self._h, _ptr(stats), _stream(stream)),
                "ramcrc_replay_table_stats_device")
         return stats
+
+    def lookup(self, keys, queries, results, counts=None, key_hash=None, keys_bytes=None,
+               n_queries=None, stream=None):
+        """What the table holds for each key, as it stands now.  keys: uint8
+        CUDA, the key buffer (keys_bytes: its length, default keys.numel());
+        queries: CUDA holding n segments.LOOKUP_KEY_DTYPE records (24 bytes
+        each, 8-byte aligned; n_queries default: its bytes / 24); results: CUDA
+        out, 32 bytes a query (segments.LOOKUP_RESULT_DTYPE), 16-byte aligned;
+        counts: int64 CUDA [5] out (segments.LOOKUP_COUNTS_DTYPE) or None;
+        key_hash: int64 CUDA [n] or None (computed).  Read-only on the table.
+        Asynchronous."""
+        if keys_bytes is None:
+            keys_bytes = 0 if keys is None else keys.numel() * keys.element_size()
+        if n_queries is None:
+            n_queries = 0 if queries is None else queries.numel() * queries.element_size() // 24
+        if n_queries and (results is None or results.numel() * results.element_size() < 32 * n_queries):
+            raise RamcrcError("ReplayTable.lookup: results is smaller than the queries")
+        if key_hash is not None and key_hash.numel() < n_queries:
+            raise RamcrcError("ReplayTable.lookup: fewer hashes than queries")
+        rc = lib().ramcrc_replay_table_lookup_device(
+            self._h, _ptr(keys) if keys_bytes else None, int(keys_bytes), _ptr(queries),
+            int(n_queries), _ptr(key_hash), _ptr(results), _ptr(counts), _stream(stream))
+        _check(rc, "ramcrc_replay_table_lookup_device")
+        return results
 
 
 # ------------------------------------------------------------ multi-GPU shard

@@ -53,6 +53,16 @@ REPLAY_TABLE_STATS_DTYPE = np.dtype([("keys", "<u8"), ("live_objects", "<u8"),
                                      ("live_tombstones", "<u8"), ("safe_version", "<u8"),
                                      ("batches", "<u8"), ("spoiled", "<u8")])
 REPLAY_TABLE_MAX_BATCHES = 65536
+# ramcrc_lookup_key, ramcrc_lookup_result, ramcrc_lookup_counts and the kinds
+# (ramcrc_replay_table_lookup_device / _host)
+LOOKUP_KEY_DTYPE = np.dtype([("table_id", "<u8"), ("key_off", "<u8"), ("key_len", "<u4"),
+                             ("reserved", "<u4")])
+LOOKUP_RESULT_DTYPE = np.dtype([("batch", "<u4"), ("record", "<u4"), ("version", "<u8"),
+                                ("kind", "<u4"), ("segment", "<u4"), ("value_off", "<u4"),
+                                ("value_len", "<u4")])
+LOOKUP_COUNTS_DTYPE = np.dtype([("objects", "<u8"), ("tombstones", "<u8"), ("absent", "<u8"),
+                                ("bad", "<u8"), ("spoiled", "<u8")])
+LOOKUP_ABSENT, LOOKUP_OBJECT, LOOKUP_TOMBSTONE, LOOKUP_BAD_KEY = 0, 1, 2, 3
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
 # (ramcrc_replay_sidelog_device / _host)
 LOG_REF_DTYPE = np.dtype([("segment", "<u4"), ("offset", "<u4")])
@@ -81,6 +91,20 @@ REPLAY_HEADER_BYTES = {LOG_ENTRY_TYPE_OBJ: 24, LOG_ENTRY_TYPE_OBJTOMB: 32,
 REPLAY_SEED = 0x5245504C   # "REPL": value bytes of segment i use seed REPLAY_SEED + i
 OBJECT_OVERHEAD = 24 + 1 + 2 + 8   # Object::Header + KeyCount + CumulativeKeyLength + key
 MIN_REPLAY_ENTRY = 1 + 1 + 12      # EntryHeader + 1 length byte + ObjectSafeVersion::Header
+
+
+def lookup_queries(keys, align=1):
+    """(key buffer uint8 [keys_bytes], queries LOOKUP_KEY_DTYPE [n]) for a list
+    of (table_id, key bytes): the keys packed one behind the other, each at a
+    multiple of `align`."""
+    q = np.zeros(len(keys), LOOKUP_KEY_DTYPE)
+    parts, at = [], 0
+    for i, (table_id, key) in enumerate(keys):
+        pad = -at % align
+        q[i] = (int(table_id), at + pad, len(key), 0)
+        parts.append(b"\0" * pad + bytes(key))
+        at += pad + len(key)
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), q
 
 
 def tablets_array(rows):
