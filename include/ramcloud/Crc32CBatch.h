@@ -407,6 +407,28 @@ class ReplayTable {
               "ramcrc_replay_table_lookup_device");
     }
 
+    /// The reply of MasterService::multiRead (src/MasterService.cc:1352-1415)
+    /// for nQueries keys, packed on the device: per key the lookup above, the
+    /// query's RejectRules as ObjectManager::rejectOperation applies them, a
+    /// MultiOp::Response::ReadPart header and, for STATUS_OK, the object's
+    /// keys and value (valueOnly: its value), back to back from d_reply until
+    /// the next part would pass replyCap (maxResponseRpcLen less the 8 bytes
+    /// of MultiOp::Response).  d_summary->returned is respHdr->count.
+    /// d_keyHash, d_rules, d_partOff and d_results are nullable.  Read-only
+    /// on the table; d_reply must not overlap an added batch.
+    void
+    multiRead(const void* d_keys, uint64_t keysBytes, const ramcrc_lookup_key* d_queries,
+              uint64_t nQueries, const uint64_t* d_keyHash, const ramcrc_reject_rules* d_rules,
+              bool valueOnly, void* d_reply, uint64_t replyCap, uint64_t* d_partOff,
+              ramcrc_lookup_result* d_results, ramcrc_read_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_read_device(table, d_keys, keysBytes, d_queries, nQueries,
+                                              d_keyHash, d_rules,
+                                              valueOnly ? RAMCRC_READ_VALUE_ONLY : 0u, d_reply,
+                                              replyCap, d_partOff, d_results, d_summary, stream),
+              "ramcrc_replay_table_read_device");
+    }
+
   private:
     static void
     check(int rc, const char* what)

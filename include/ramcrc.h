@@ -782,6 +782,123 @@ int ramcrc_replay_table_lookup_host(ramcrc_replay_table_host* t, const void* key
                                     const uint64_t* key_hash, ramcrc_lookup_result* results,
                                     ramcrc_lookup_counts* counts);
 
+/* A multi-read's reply: the loop of MasterService::multiRead
+ * (src/MasterService.cc:1352-1415) over ObjectManager::readObject
+ * (src/ObjectManager.cc:324-369) and rejectOperation (:2893-2907), against the
+ * replay table.  The call looks every key up, applies the query's RejectRules,
+ * and packs MultiOp::Response::ReadPart headers and object data back to back
+ * into d_reply until the reply would pass reply_cap.  Rules marked "ours"
+ * cover what the reference leaves uninitialised or where the packed query
+ * form differs from the wire's.
+ *
+ * Lookup.  Queries, the key buffer, hashes, key identity, the bad-query test
+ * and the moment of the answer are exactly ramcrc_replay_table_lookup_device's.
+ * d_results, when not NULL, receives bit for bit what that call would write.
+ * The call reads the table and the added batches' segments and writes only
+ * its outputs.
+ *
+ * Status per query, in this order.
+ *   - Ours: a bad query (RAMCRC_LOOKUP_BAD_KEY, or d_rules[q].reserved != 0)
+ *     gets STATUS_REQUEST_FORMAT_ERROR (9), version 0, length 0, and the call
+ *     goes on with the next query.
+ *   - ABSENT or TOMBSTONE: STATUS_OBJECT_DOESNT_EXIST (3), before any rule is
+ *     looked at (:341-342).  Ours: version 0, length 0 (the reference leaves
+ *     both unset).
+ *   - OBJECT with version v: version = v, then rejectOperation(rules, v)
+ *     verbatim: v == 0 (VERSION_NONEXISTENT) gives 3 if doesnt_exist, else
+ *     OK; exists gives STATUS_OBJECT_EXISTS (4); version_le_given && v <=
+ *     given_version gives STATUS_WRONG_VERSION (5); version_ne_given && v !=
+ *     given_version gives 5; otherwise STATUS_OK (0).  A rule byte is set when
+ *     it is not 0.  A rejected object keeps its version; ours: its length is 0.
+ *   d_rules = NULL: no rule is set for any query.  STATUS_UNKNOWN_TABLET is the
+ *   tablet manager's: the caller applies it before the call.
+ *
+ * Part.  A part is MultiOp::Response::ReadPart (src/WireFormat.h:1140-1155),
+ * packed, 16 bytes little-endian: {u32 status, u64 version, u32 length}.  Only
+ * a STATUS_OK part is followed by `length` data bytes: by default the winner's
+ * payload [24, payload length) -- key count, cumulative key lengths, keys and
+ * value, as appendKeysAndValueToBuffer writes them (src/Object.cc:279-291) --,
+ * with RAMCRC_READ_VALUE_ONLY the value_len bytes at value_off (possibly
+ * none).  An object whose keys run past its payload has value_len 0 and still
+ * sends its payload from 24 by default.  Parts lie back to back in query
+ * order from d_reply + 0, so a part may start at any byte.  d_part_off[q]
+ * (nullable) is the offset of query q's part, or RAMCRC_READ_NONE if q was not
+ * returned.
+ *
+ * Truncation (:1364-1375).  With end_q the offset just past part q, the
+ * returned queries are the leading ones with end_q <= reply_cap; `returned`
+ * is their number (respHdr->count) and reply_bytes the last such end_q (0 when
+ * none).  reply_cap is the caller's maxResponseRpcLen minus the 8-byte
+ * MultiOp::Response header it writes itself; the reference's own test
+ * (src/MasterServiceTest.cc:1450-1484) returns exactly one 1-byte-key,
+ * 50-byte-value object at limit 78 = 8 + 16 + 54.  No byte of d_reply at or
+ * past reply_bytes is written.  Ours: the summary's counters cover returned
+ * parts only.  value_bytes and key_bytes are PerfStats' readObjectBytes
+ * (getValueLength) and readKeyBytes (getKeysAndValueLength - getValueLength)
+ * of the returned OK parts, in either mode.
+ *
+ * Queries may repeat: every copy gets its own part and its own data.
+ * n_queries = 0 writes a zeroed summary and nothing else.  On a spoiled table
+ * d_reply, d_part_off and d_results stay untouched, the summary is all zero
+ * with spoiled = 1, and no new refusal is raised: the lookup's rule.
+ *
+ * RAMCRC_EINVAL before any launch: unknown flag bits; d_summary or d_queries
+ * NULL with n_queries > 0; d_reply NULL with
+ * reply_cap > 0; misaligned d_queries (8), d_rules (8), d_results (16),
+ * d_part_off (8) or d_summary (8); n_queries >= 2^32 - 1.  d_reply and d_keys
+ * need no alignment.  d_reply must not overlap any added batch's segments,
+ * the key buffer or another argument; the call cannot check this.  Data
+ * bytes are fetched as the aligned 16-byte words that hold at least one of
+ * them.
+ *
+ * Scratch comes from the context: 32 + 8 * ceil(n_queries / 256) words and 4 *
+ * n_queries entries.  After ramcrc_ctx_reserve(ctx, 32 + 8 * ceil(n / 256),
+ * 4 * n), or after any earlier call on the context that reserved as much, a
+ * read of up to n queries does not allocate.  The call is stream-ordered and
+ * asynchronous; lifetime and concurrency are the table's. */
+typedef struct ramcrc_reject_rules {   /* RejectRules, src/RejectRules.h:41-47, padded to 16 bytes */
+    uint64_t given_version;
+    uint8_t  doesnt_exist, exists, version_le_given, version_ne_given;
+    uint32_t reserved;                 /* must be 0 */
+} ramcrc_reject_rules;
+
+#define RAMCRC_READ_VALUE_ONLY 1u      /* readObject's valueOnly; default: keys and value, as multiRead sends */
+#define RAMCRC_READ_NONE 0xFFFFFFFFFFFFFFFFull
+
+#define RAMCRC_STATUS_OK 0u                     /* src/Status.h */
+#define RAMCRC_STATUS_OBJECT_DOESNT_EXIST 3u
+#define RAMCRC_STATUS_OBJECT_EXISTS 4u
+#define RAMCRC_STATUS_WRONG_VERSION 5u
+#define RAMCRC_STATUS_REQUEST_FORMAT_ERROR 9u
+
+typedef struct ramcrc_read_summary {
+    uint64_t returned;        /* respHdr->count: leading queries whose part is in the reply */
+    uint64_t reply_bytes;     /* end of the last returned part */
+    uint64_t ok, doesnt_exist, object_exists, wrong_version, bad;  /* returned parts by status */
+    uint64_t value_bytes;     /* PerfStats readObjectBytes of the returned OK parts */
+    uint64_t key_bytes;       /* readKeyBytes: keysAndValueLength - valueLength, same parts */
+    uint64_t spoiled;
+} ramcrc_read_summary;
+
+int ramcrc_replay_table_read_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* d_queries, uint64_t n_queries,
+                                    const uint64_t* d_key_hash /* nullable */,
+                                    const ramcrc_reject_rules* d_rules /* nullable: no rules */,
+                                    uint32_t flags, void* d_reply, uint64_t reply_cap,
+                                    uint64_t* d_part_off /* nullable, one per query */,
+                                    ramcrc_lookup_result* d_results /* nullable */,
+                                    ramcrc_read_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                  const ramcrc_lookup_key* queries, uint64_t n_queries,
+                                  const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                  uint32_t flags, void* reply, uint64_t reply_cap,
+                                  uint64_t* part_off, ramcrc_lookup_result* results,
+                                  ramcrc_read_summary* summary);
+
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,
  * :840-867), and where each record then lies.  The call is

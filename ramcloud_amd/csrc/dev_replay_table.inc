@@ -1,7 +1,8 @@
 // The persistent replay table (ramcrc_replay_table_*): k_rtab_zero,
 // k_rtab_open, k_rtab_insert, k_rtab_pick (an add), k_rtab_tiles, k_rtab_scan,
 // k_rtab_emit (a live query), k_rtab_stats (DESIGN.md 5.11), k_rtab_lookup
-// (a lookup by key, DESIGN.md 5.13).
+// (a lookup by key, DESIGN.md 5.13), k_rtab_read_size, k_rtab_read_scan,
+// k_rtab_read_gather (a multi-read's reply, DESIGN.md 5.14).
 // Part of ramcrc_device.hip (one translation unit: the kernels share the
 // g_tab tables, LDS layouts and templates without relocatable device code).
 // Included only from there, after dev_resolve.inc; not a standalone header.
@@ -502,6 +503,82 @@ __device__ __forceinline__ int look_counter(uint32_t kind)
            : kind == RAMCRC_LOOKUP_ABSENT ? 2 : 3;
 }
 
+// The winning object's payload, for a caller that goes on to read it.
+struct LookHit {
+    uint64_t pay;            // its address
+    uint32_t len;            // its length
+    ramcrc_look::Value v;    // the value's place in it
+};
+
+// Query i's answer: the probe k_rtab_lookup and k_rtab_read_size share.
+template <bool kGiven>
+__device__ __forceinline__ ramcrc_lookup_result rtab_probe(const RtabDesc& a, const LookDesc& q,
+                                                           uint64_t i, LookHit* hit)
+{
+    const uint64_t mask = a.nslots - 1;
+    const uint64_t table_id = q.queries[3 * i], off = q.queries[3 * i + 1];
+    const uint64_t lr = q.queries[3 * i + 2];
+    const uint32_t len = uint32_t(lr);
+    ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
+    if (ramcrc_look::bad_query(off, len, uint32_t(lr >> 32), q.keys_bytes))
+        return res;
+    res.kind = RAMCRC_LOOKUP_ABSENT;
+    const uint64_t addr = q.keys + off;
+    uint64_t hash;
+    if constexpr (kGiven)
+        hash = q.key_hash[i];
+    else
+        hash = part_key_hash(table_id, addr, len);
+    // bounded by the slot count, as the insert's probe is
+    uint64_t s = hash & mask;
+    for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+        const uint64_t c = *rtab_word(a, s, 2);
+        if (c == 0)
+            break;
+        const ResKey k = rtab_key_of(a.batches[c >> 32], (c & 0xFFFFFFFFull) - 1);
+        if (k.table_id != table_id || k.len != len || !res_bytes_equal(k.addr, addr, len))
+            continue;
+        const uint64_t pick = *rtab_word(a, s, 1);
+        if (pick == 0)   // (between adds every claimed slot has one)
+            break;
+        const uint64_t rank = ~pick;   // as rtab_winner decodes it
+        const uint32_t wb = uint32_t(rank >> 32) & 0xFFFFu, wr = uint32_t(rank);
+        const RtabBatch& b = a.batches[wb];
+        const u32x4 r = b.entries[wr];
+        const uint32_t pay = r.y + 1 + ((r.w >> 6) & 3) + 1;
+        const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
+        res.ref = ramcrc_replay_ref{wb, wr};
+        res.version = ramcrc_res::version(r.w & 0x3f, rd);
+        if ((rank >> 48) & 1) {
+            const ramcrc_look::Value v = ramcrc_look::object_value(r.z, rd);
+            res.kind = RAMCRC_LOOKUP_OBJECT;
+            res.segment = r.x;
+            res.value_off = pay + v.off;
+            res.value_len = v.len;
+            *hit = LookHit{rd.pay, r.z, v};
+        } else {
+            res.kind = RAMCRC_LOOKUP_TOMBSTONE;
+        }
+        break;
+    }
+    return res;
+}
+
+__device__ __forceinline__ void look_store(const LookDesc& q, uint64_t i, const ramcrc_lookup_result& res)
+{
+    u32x4 lo, hi;
+    lo.x = res.ref.batch;
+    lo.y = res.ref.record;
+    lo.z = uint32_t(res.version);
+    lo.w = uint32_t(res.version >> 32);
+    hi.x = res.kind;
+    hi.y = res.segment;
+    hi.z = res.value_off;
+    hi.w = res.value_len;
+    q.results[2 * i] = lo;
+    q.results[2 * i + 1] = hi;
+}
+
 template <bool kGiven>
 __global__ __launch_bounds__(kPartThreads) void k_rtab_lookup(RtabDesc a, LookDesc q)
 {
@@ -512,68 +589,15 @@ __global__ __launch_bounds__(kPartThreads) void k_rtab_lookup(RtabDesc a, LookDe
             *q.counts_out = ramcrc_lookup_counts{0, 0, 0, 0, 1};
         return;
     }
-    const uint64_t mask = a.nslots - 1;
     uint32_t cnt[kLookCounters] = {};   // (a lane takes fewer than 2^32 queries)
     for (uint64_t i0 = uint64_t(blockIdx.x) * kPartThreads; i0 < q.nq;
          i0 += uint64_t(gridDim.x) * kPartThreads) {
         const uint64_t i = i0 + threadIdx.x;
         if (i >= q.nq)
             continue;
-        const uint64_t table_id = q.queries[3 * i], off = q.queries[3 * i + 1];
-        const uint64_t lr = q.queries[3 * i + 2];
-        const uint32_t len = uint32_t(lr);
-        ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
-        if (!ramcrc_look::bad_query(off, len, uint32_t(lr >> 32), q.keys_bytes)) {
-            res.kind = RAMCRC_LOOKUP_ABSENT;
-            const uint64_t addr = q.keys + off;
-            uint64_t hash;
-            if constexpr (kGiven)
-                hash = q.key_hash[i];
-            else
-                hash = part_key_hash(table_id, addr, len);
-            // bounded by the slot count, as the insert's probe is
-            uint64_t s = hash & mask;
-            for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
-                const uint64_t c = *rtab_word(a, s, 2);
-                if (c == 0)
-                    break;
-                const ResKey k = rtab_key_of(a.batches[c >> 32], (c & 0xFFFFFFFFull) - 1);
-                if (k.table_id != table_id || k.len != len || !res_bytes_equal(k.addr, addr, len))
-                    continue;
-                const uint64_t pick = *rtab_word(a, s, 1);
-                if (pick == 0)   // (between adds every claimed slot has one)
-                    break;
-                const uint64_t rank = ~pick;   // as rtab_winner decodes it
-                const uint32_t wb = uint32_t(rank >> 32) & 0xFFFFu, wr = uint32_t(rank);
-                const RtabBatch& b = a.batches[wb];
-                const u32x4 r = b.entries[wr];
-                const uint32_t pay = r.y + 1 + ((r.w >> 6) & 3) + 1;
-                const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
-                res.ref = ramcrc_replay_ref{wb, wr};
-                res.version = ramcrc_res::version(r.w & 0x3f, rd);
-                if ((rank >> 48) & 1) {
-                    const ramcrc_look::Value v = ramcrc_look::object_value(r.z, rd);
-                    res.kind = RAMCRC_LOOKUP_OBJECT;
-                    res.segment = r.x;
-                    res.value_off = pay + v.off;
-                    res.value_len = v.len;
-                } else {
-                    res.kind = RAMCRC_LOOKUP_TOMBSTONE;
-                }
-                break;
-            }
-        }
-        u32x4 lo, hi;
-        lo.x = res.ref.batch;
-        lo.y = res.ref.record;
-        lo.z = uint32_t(res.version);
-        lo.w = uint32_t(res.version >> 32);
-        hi.x = res.kind;
-        hi.y = res.segment;
-        hi.z = res.value_off;
-        hi.w = res.value_len;
-        q.results[2 * i] = lo;
-        q.results[2 * i + 1] = hi;
+        LookHit hit;
+        const ramcrc_lookup_result res = rtab_probe<kGiven>(a, q, i, &hit);
+        look_store(q, i, res);
 #pragma unroll
         for (int k = 0; k < kLookCounters; k++)
             cnt[k] += look_counter(res.kind) == k;
@@ -608,6 +632,325 @@ __global__ __launch_bounds__(kPartThreads) void k_rtab_lookup(RtabDesc a, LookDe
         __threadfence();
         reinterpret_cast<unsigned long long*>(q.counts_out)[t] =
             t < kLookCounters ? atomicAdd(&q.counts[t], 0ull) : 0ull;   // spoiled: 0
+    }
+}
+
+// ------------------------------------------------------------- k_rtab_read_*
+// A multi-read's reply (ramcrc_replay_table_read_device, DESIGN.md 5.14), in
+// the three launches of the live query; no workgroup waits for another:
+//   k_rtab_read_size    one query per lane in tiles of kPartThreads: the
+//                       lookup's probe, the status and the part's data range
+//                       (read_rules.h) into four scratch words per query, and
+//                       per tile the sums of the part sizes, the statuses and
+//                       the value and key bytes, by one atomic per wave and sum
+//                       (the call zeroes them): no barrier, as in the lookup;
+//   k_rtab_read_scan    one workgroup: the tile sums become exclusive offsets;
+//                       the tiles whose end lies within reply_cap count whole,
+//                       the first one that does not is scanned query by query
+//                       for the truncation point; then the summary;
+//   k_rtab_read_gather  per tile the offsets of its parts, d_part_off, the
+//                       headers and the data of the returned parts.
+// The gather is k_app_copy with the sources in random order: a part's data
+// goes through app_copy (aligned 16-byte stores for the destination's full
+// granules, byte stores around them), by 8 lanes below kAppBigMin, by a wave
+// below kAppGroupMin, by the workgroup above; the 16 header bytes, which may
+// start at any byte and share granules with both neighbours, are byte stores,
+// two by each of the part's 8 lanes.
+constexpr uint32_t kReadRecWords = 4;    // scratch per query: source, version, length | status << 32,
+                                         // value bytes | key bytes << 32
+constexpr uint32_t kReadTileWords = 4;   // scratch per tile: size (then the offset), statuses, value, key bytes
+constexpr int kReadStatuses = 5;         // ok, doesnt_exist, object_exists, wrong_version, bad
+constexpr uint32_t kReadScanPer = 2;     // tiles per lane and step of the scan
+constexpr int kReadCountBits = 12;       // a tile's count of one status: at most kPartThreads
+static_assert(kPartThreads < (1 << kReadCountBits) && kReadStatuses * kReadCountBits <= 64, "tile counts");
+static_assert(kAppCopyThreads == kPartThreads, "the gather posts one part per lane of a tile");
+static_assert(sizeof(ramcrc_reject_rules) == 16 && sizeof(ramcrc_read_summary) == 80, "read ABI");
+
+struct ReadDesc {
+    const uint64_t* rules;          // nullable: two words a query
+    uint32_t flags;
+    uint64_t reply;
+    uint64_t cap;
+    uint64_t* part_off;             // nullable
+    ramcrc_read_summary* summary;
+    uint64_t* rec;                  // scratch [kReadRecWords * nq]
+    uint64_t* tile;                 // scratch [kReadTileWords * tiles]
+    unsigned long long* head;       // scratch line: [0] the returned queries, written by the scan
+};
+
+// ramcrc_read_summary's field of a status, from `ok` on.
+__device__ __forceinline__ int read_counter(uint32_t status)
+{
+    return status == ramcrc_read::kStatusOk ? 0 : status == ramcrc_read::kStatusDoesntExist ? 1
+           : status == ramcrc_read::kStatusExists ? 2 : status == ramcrc_read::kStatusWrongVersion ? 3 : 4;
+}
+
+// The sum of v over the workgroup, in every lane; red: kPartThreads / kWaveSize words.
+__device__ __forceinline__ uint64_t rtab_block_sum(uint64_t v, uint64_t* red)
+{
+    unsigned long long s = v;
+#pragma unroll
+    for (int d = 1; d < kWaveSize; d <<= 1)
+        s += __shfl_xor(s, d);
+    if ((threadIdx.x & (kWaveSize - 1)) == 0)
+        red[threadIdx.x / kWaveSize] = s;
+    __syncthreads();
+    uint64_t tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kPartThreads / kWaveSize; w++)
+        tot += red[w];
+    __syncthreads();   // red is free again
+    return tot;
+}
+
+template <bool kGiven>
+__global__ __launch_bounds__(kPartThreads) void k_rtab_read_size(RtabDesc a, LookDesc q, ReadDesc r)
+{
+    namespace rr = ramcrc_read;
+    if (rtab_refused(a))
+        return;
+    const uint64_t ntiles = (q.nq + kPartThreads - 1) / kPartThreads;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t i = tile * kPartThreads + threadIdx.x;
+        uint64_t size = 0, cnt = 0, vbytes = 0, kbytes = 0;
+        if (i < q.nq) {
+            LookHit hit{0ull, 0u, ramcrc_look::Value{0u, 0u}};
+            const ramcrc_lookup_result res = rtab_probe<kGiven>(a, q, i, &hit);
+            if (q.results)
+                look_store(q, i, res);
+            rr::Rules ru = rr::no_rules();
+            if (r.rules)
+                ru = rr::Rules{r.rules[2 * i], r.rules[2 * i + 1]};
+            uint64_t version = res.version;
+            const uint32_t st = rr::status(rr::bad_rules(ru), res.kind, ru, &version);
+            rr::Data d{0u, 0u};
+            uint64_t src = 0;
+            if (st == rr::kStatusOk) {
+                d = rr::data_range(r.flags, hit.len, hit.v);
+                src = hit.pay + d.off;
+                vbytes = hit.v.len;
+                kbytes = rr::key_bytes(hit.len, hit.v);
+            }
+            size = rr::part_size(st, d.len);
+            cnt = 1ull << (kReadCountBits * read_counter(st));
+            uint64_t* const rec = r.rec + kReadRecWords * i;
+            rec[0] = src;
+            rec[1] = version;
+            rec[2] = uint64_t(d.len) | (uint64_t(st) << 32);
+            rec[3] = vbytes | (kbytes << 32);
+        }
+        // the tile's sums, which the call zeroed: one atomic per wave and sum,
+        // so that no wave waits for another, as in the lookup
+        uint64_t sums[kReadTileWords] = {size, cnt, vbytes, kbytes};
+#pragma unroll
+        for (uint32_t k = 0; k < kReadTileWords; k++) {
+            unsigned long long v = sums[k];
+#pragma unroll
+            for (int d = 1; d < kWaveSize; d <<= 1)
+                v += __shfl_xor(v, d);
+            if ((threadIdx.x & (kWaveSize - 1)) == 0 && v)
+                atomicAdd(reinterpret_cast<unsigned long long*>(r.tile + kReadTileWords * tile + k), v);
+        }
+    }
+}
+
+// One workgroup.  Part sizes are at least 16, so the ends of the parts grow
+// strictly and the returned queries are a prefix: whole tiles, then a prefix
+// of one tile.
+__global__ __launch_bounds__(kPartThreads) void k_rtab_read_scan(RtabDesc a, LookDesc q, ReadDesc r)
+{
+    namespace rr = ramcrc_read;
+    __shared__ uint64_t wsum[kPartThreads / kWaveSize];
+    __shared__ unsigned long long cut_s;
+    const uint32_t t = threadIdx.x;
+    if (rtab_refused(a)) {
+        if (t == 0) {
+            ramcrc_read_summary sm{};
+            sm.spoiled = 1;
+            *r.summary = sm;
+        }
+        return;
+    }
+    const uint64_t ntiles = (q.nq + kPartThreads - 1) / kPartThreads;
+    if (t == 0)
+        cut_s = ntiles;
+    __syncthreads();
+    uint64_t carry = 0, vbytes = 0, kbytes = 0, cut = ntiles;
+    uint64_t cnt[kReadStatuses] = {};
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += uint64_t(kPartThreads) * kReadScanPer) {
+        // kReadScanPer neighbouring tiles a lane, their loads in flight together
+        const uint64_t tl0 = t0 + uint64_t(t) * kReadScanPer;
+        uint64_t v[kReadScanPer], sum = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kReadScanPer; k++) {
+            v[k] = tl0 + k < ntiles ? r.tile[kReadTileWords * (tl0 + k)] : 0ull;
+            sum += v[k];
+        }
+        uint64_t tot;
+        uint64_t base = carry + part_block_excl(sum, wsum, &tot);
+#pragma unroll
+        for (uint32_t k = 0; k < kReadScanPer; k++) {
+            const uint64_t tl = tl0 + k;
+            if (tl >= ntiles)
+                break;
+            uint64_t* const ts = r.tile + kReadTileWords * tl;
+            ts[0] = base;
+            if (base + v[k] <= r.cap) {
+                const uint64_t c = ts[1];
+#pragma unroll
+                for (int j = 0; j < kReadStatuses; j++)
+                    cnt[j] += (c >> (kReadCountBits * j)) & ((1u << kReadCountBits) - 1);
+                vbytes += ts[2];
+                kbytes += ts[3];
+            } else if (tl < cut) {
+                cut = tl;
+            }
+            base += v[k];
+        }
+        carry += tot;
+    }
+    if (cut < ntiles)
+        atomicMin(&cut_s, static_cast<unsigned long long>(cut));
+    __syncthreads();   // the cut, and every tile's offset
+    cut = cut_s;
+    uint64_t returned = q.nq, bytes = carry;
+    if (cut < ntiles) {
+        // the tile the reply ends in: its parts one by one
+        const uint64_t i = cut * kPartThreads + t;
+        uint64_t size = 0, w2 = 0, w3 = 0;
+        if (i < q.nq) {
+            w2 = r.rec[kReadRecWords * i + 2];
+            w3 = r.rec[kReadRecWords * i + 3];
+            size = rr::part_size(uint32_t(w2 >> 32), uint32_t(w2));
+        }
+        uint64_t tot;
+        const uint64_t base = r.tile[kReadTileWords * cut];
+        const uint64_t off = base + part_block_excl(size, wsum, &tot);
+        const bool in = i < q.nq && off + size <= r.cap;
+        if (in) {
+            const uint32_t st = uint32_t(w2 >> 32);
+#pragma unroll
+            for (int k = 0; k < kReadStatuses; k++)
+                cnt[k] += read_counter(st) == k;
+            if (st == rr::kStatusOk) {
+                vbytes += uint32_t(w3);
+                kbytes += w3 >> 32;
+            }
+        }
+        const uint64_t n_in = rtab_block_sum(in ? 1ull : 0ull, wsum);
+        returned = cut * kPartThreads + n_in;
+        bytes = base + rtab_block_sum(in ? size : 0ull, wsum);
+    }
+    uint64_t sums[kReadStatuses + 2];
+#pragma unroll
+    for (int k = 0; k < kReadStatuses; k++)
+        sums[k] = rtab_block_sum(cnt[k], wsum);
+    sums[kReadStatuses] = rtab_block_sum(vbytes, wsum);
+    sums[kReadStatuses + 1] = rtab_block_sum(kbytes, wsum);
+    if (t == 0) {
+        ramcrc_read_summary sm{};
+        sm.returned = returned;
+        sm.reply_bytes = bytes;
+        sm.ok = sums[0];
+        sm.doesnt_exist = sums[1];
+        sm.object_exists = sums[2];
+        sm.wrong_version = sums[3];
+        sm.bad = sums[4];
+        sm.value_bytes = sums[5];
+        sm.key_bytes = sums[6];
+        *r.summary = sm;
+        r.head[0] = returned;
+    }
+}
+
+__global__ __launch_bounds__(kPartThreads) void k_rtab_read_gather(RtabDesc a, LookDesc q, ReadDesc r)
+{
+    namespace rr = ramcrc_read;
+    typedef __attribute__((address_space(1))) uint8_t gw8;
+    __shared__ uint64_t wsum[kPartThreads / kWaveSize];
+    __shared__ uint64_t ssrc[kPartThreads], sdst[kPartThreads];   // sdst: behind the header; 0: not returned
+    __shared__ uint64_t sh0[kPartThreads], sh1[kPartThreads];     // the header's words
+    __shared__ uint32_t slen[kPartThreads], sbig[kPartThreads];
+    __shared__ uint32_t nbig[2];   // by tile parity, as in k_app_copy
+    if (rtab_refused(a))
+        return;
+    const uint64_t returned = r.head[0];
+    const uint64_t ntiles = (q.nq + kPartThreads - 1) / kPartThreads;
+    const uint32_t t = threadIdx.x;
+    if (t == 0)
+        nbig[0] = nbig[1] = 0;
+    uint32_t par = 0;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1u) {
+        const uint64_t i = tile * kPartThreads + t;
+        if (tile * kPartThreads >= returned) {
+            // nothing of this tile is in the reply (the same for every lane)
+            if (r.part_off && i < q.nq)
+                r.part_off[i] = RAMCRC_READ_NONE;
+            par ^= 1u;   // (no tile was posted: the parity stays)
+            continue;
+        }
+        __syncthreads();   // the previous tile's copies have read their descriptors and its count
+        if (t == 0)
+            nbig[par ^ 1u] = 0;   // the next tile's
+        uint64_t src = 0, dst = 0, size = 0, version = 0;
+        uint32_t len = 0, st = 0;
+        if (i < q.nq) {
+            const uint64_t* const rec = r.rec + kReadRecWords * i;
+            const uint64_t w2 = rec[2];
+            src = rec[0];
+            version = rec[1];
+            len = uint32_t(w2);
+            st = uint32_t(w2 >> 32);
+            size = rr::part_size(st, len);
+        }
+        uint64_t tot;
+        const uint64_t off = r.tile[kReadTileWords * tile] + part_block_excl(size, wsum, &tot);
+        // (the scan returned only parts that fit; checked again as the last
+        // thing between a stale word and a stray store)
+        const bool in = i < returned && off + size <= r.cap;
+        if (r.part_off && i < q.nq)
+            r.part_off[i] = in ? off : RAMCRC_READ_NONE;
+        uint64_t h0 = 0, h1 = 0;
+        if (in) {
+            rr::header_words(st, version, len, &h0, &h1);
+            dst = r.reply + off + rr::kPartHeader;
+        } else {
+            len = 0;
+        }
+        ssrc[t] = src;
+        sdst[t] = dst;
+        sh0[t] = h0;
+        sh1[t] = h1;
+        slen[t] = len;
+        if (len >= kAppBigMin)
+            sbig[atomicAdd(&nbig[par], 1u)] = t;
+        __syncthreads();
+        const uint32_t g = t >> 3, sub = t & 7;
+        for (uint32_t j = g; j < kPartThreads; j += kPartThreads / 8) {
+            const uint64_t d = sdst[j];
+            if (!d)
+                continue;
+            const uint64_t hw = sub < 4 ? sh0[j] : sh1[j];
+            const uint32_t two = uint32_t(hw >> (16 * (sub & 3)));
+            *reinterpret_cast<gw8*>(d - rr::kPartHeader + 2 * sub) = uint8_t(two);
+            *reinterpret_cast<gw8*>(d - rr::kPartHeader + 2 * sub + 1) = uint8_t(two >> 8);
+            const uint32_t L = slen[j];
+            if (L && L <= kAppShortMax)
+                app_copy<8, 2>(ssrc[j], d, L, sub);
+            else if (L > kAppShortMax && L < kAppBigMin)
+                app_copy<8, 8>(ssrc[j], d, L, sub);
+        }
+        const uint32_t nb = nbig[par], wv = t >> 6, ln = t & 63;
+        for (uint32_t b = wv; b < nb; b += kPartThreads / kWaveSize) {
+            const uint32_t j = sbig[b];
+            if (slen[j] < kAppGroupMin)
+                app_copy<kWaveSize, 4>(ssrc[j], sdst[j], slen[j], ln);
+        }
+        for (uint32_t b = 0; b < nb; b++) {
+            const uint32_t j = sbig[b];
+            if (slen[j] >= kAppGroupMin)
+                app_copy<kPartThreads, 4>(ssrc[j], sdst[j], slen[j], t);
+        }
     }
 }
 

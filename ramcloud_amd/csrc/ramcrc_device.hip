@@ -62,7 +62,7 @@
 //   dev_partition.inc  k_part_* (key hash, tablet lookup, liveness: the placement list)
 //   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
 //   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table,
-//                         and its lookup by key)
+//                         its lookup by key and a multi-read's reply)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -81,6 +81,7 @@
 #include "murmur3.h"
 #include "partition_rules.h"
 #include "lookup_rules.h"
+#include "read_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "ramcrc.h"
@@ -1479,6 +1480,73 @@ int ramcrc_replay_table_lookup_device(ramcrc_replay_table* t, const void* d_keys
     else
         hipLaunchKernelGGL(k_rtab_lookup<false>, grid, dim3(kPartThreads), 0, s, a, q);
     HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_read_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* d_queries, uint64_t n_queries,
+                                    const uint64_t* d_key_hash, const ramcrc_reject_rules* d_rules,
+                                    uint32_t flags, void* d_reply, uint64_t reply_cap,
+                                    uint64_t* d_part_off, ramcrc_lookup_result* d_results,
+                                    ramcrc_read_summary* d_summary, void* stream)
+{
+    if (!t || n_queries >= 0xFFFFFFFFull || (flags & ~RAMCRC_READ_VALUE_ONLY) ||
+        (n_queries && (!d_queries || !d_summary)) || (keys_bytes && !d_keys) ||
+        (reply_cap && !d_reply))
+        return RAMCRC_EINVAL;
+    const uint64_t K = reinterpret_cast<uint64_t>(d_keys), R = reinterpret_cast<uint64_t>(d_reply);
+    if ((reinterpret_cast<uint64_t>(d_queries) & 7) || (reinterpret_cast<uint64_t>(d_rules) & 7) ||
+        (reinterpret_cast<uint64_t>(d_results) & 15) || (reinterpret_cast<uint64_t>(d_part_off) & 7) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || K > UINT64_MAX - keys_bytes ||
+        R > UINT64_MAX - reply_cap)
+        return RAMCRC_EINVAL;
+    if (!d_summary)
+        return RAMCRC_OK;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: a line for the scan's word to the gather, then the tile sums,
+    // in the chunk-partial buffer; the per-query words in the plan buffer
+    // (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_queries + kPartThreads - 1) / kPartThreads;
+    int rc = reserve_locked(c, kLookCountWords + 2 * kReadTileWords * ntiles, kReadRecWords * n_queries);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    LookDesc q{};
+    q.keys = K;
+    q.keys_bytes = keys_bytes;
+    q.queries = reinterpret_cast<const uint64_t*>(d_queries);
+    q.nq = n_queries;
+    q.key_hash = d_key_hash;
+    q.results = reinterpret_cast<u32x4*>(d_results);
+    ReadDesc r{};
+    r.rules = reinterpret_cast<const uint64_t*>(d_rules);
+    r.flags = flags;
+    r.reply = R;
+    r.cap = reply_cap;
+    r.part_off = d_part_off;
+    r.summary = d_summary;
+    r.rec = c->plan_local;
+    r.head = reinterpret_cast<unsigned long long*>(c->partials);
+    r.tile = reinterpret_cast<uint64_t*>(c->partials + kLookCountWords);
+    const dim3 grid(rtab_grid(c, n_queries, kPartThreads));
+    if (n_queries) {
+        HIPCHK(hipMemsetAsync(r.tile, 0, kReadTileWords * ntiles * sizeof(uint64_t), s));
+        if (d_key_hash)
+            hipLaunchKernelGGL(k_rtab_read_size<true>, grid, dim3(kPartThreads), 0, s, a, q, r);
+        else
+            hipLaunchKernelGGL(k_rtab_read_size<false>, grid, dim3(kPartThreads), 0, s, a, q, r);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rtab_read_scan, dim3(1), dim3(kPartThreads), 0, s, a, q, r);
+    HIPCHK(hipGetLastError());
+    if (n_queries) {
+        hipLaunchKernelGGL(k_rtab_read_gather, grid, dim3(kPartThreads), 0, s, a, q, r);
+        HIPCHK(hipGetLastError());
+    }
     return RAMCRC_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "murmur3.h"
 #include "partition_rules.h"
 #include "lookup_rules.h"
+#include "read_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 
@@ -900,13 +901,67 @@ int ramcrc_replay_table_stats_host(ramcrc_replay_table_host* t, ramcrc_replay_ta
 
 // What the table holds for a key (the rules of lookup_rules.h): the add's
 // probe without the writes, then the winner's record for the version and the
-// value's place.
+// value's place.  *pay and *pay_len: the winning object's payload.
+namespace {
+struct LookRd {
+    const uint8_t* pay;
+    uint32_t u8(uint32_t o) const { return pay[o]; }
+    uint32_t u16(uint32_t o) const { return ld16(pay + o); }
+    uint32_t u32(uint32_t o) const { return ld32(pay + o); }
+    uint64_t u64(uint32_t o) const { return ld64(pay + o); }
+};
+
+ramcrc_lookup_result look_one(const ramcrc_replay_table_host* t, const uint8_t* kb, uint64_t keys_bytes,
+                              const ramcrc_lookup_key& q, const uint64_t* hash_given,
+                              const uint8_t** pay, uint32_t* pay_len, ramcrc_look::Value* value)
+{
+    namespace rl = ramcrc_look;
+    if (rl::bad_query(q.key_off, q.key_len, q.reserved, keys_bytes))
+        return rl::no_result(RAMCRC_LOOKUP_BAD_KEY);
+    ramcrc_lookup_result res = rl::no_result(RAMCRC_LOOKUP_ABSENT);
+    const uint64_t mask = t->slots.size() - 1;
+    const uint8_t* const key = q.key_len ? kb + q.key_off : nullptr;
+    const uint64_t hash = hash_given ? *hash_given : ramcrc::key_hash(q.table_id, key, q.key_len);
+    uint64_t s = hash & mask;
+    for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+        const ramcrc_replay_table_host::Slot& sl = t->slots[s];
+        if (!sl.claim)
+            break;
+        if (sl.table_id != q.table_id || sl.key_len != q.key_len ||
+            (q.key_len && memcmp(sl.key, key, q.key_len)))
+            continue;
+        const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
+        const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
+        const ramcrc_seg_entry& r = bt.entries[wr];
+        const uint32_t po = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+        res.ref = ramcrc_replay_ref{wb, wr};
+        res.version = sl.version;
+        if ((sl.rank >> 48) & 1) {
+            const LookRd rd{bt.base + r.segment * bt.stride + po};
+            const rl::Value v = rl::object_value(r.length, rd);
+            res.kind = RAMCRC_LOOKUP_OBJECT;
+            res.segment = r.segment;
+            res.value_off = po + v.off;
+            res.value_len = v.len;
+            if (pay) {
+                *pay = rd.pay;
+                *pay_len = r.length;
+                *value = v;
+            }
+        } else {
+            res.kind = RAMCRC_LOOKUP_TOMBSTONE;
+        }
+        break;
+    }
+    return res;
+}
+}  // namespace
+
 int ramcrc_replay_table_lookup_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
                                     const ramcrc_lookup_key* queries, uint64_t n_queries,
                                     const uint64_t* key_hash, ramcrc_lookup_result* results,
                                     ramcrc_lookup_counts* counts)
 {
-    namespace rl = ramcrc_look;
     if (!t || n_queries >= 0xFFFFFFFFull || (n_queries && (!queries || !results)) ||
         (keys_bytes && !keys))
         return RAMCRC_EINVAL;
@@ -915,59 +970,95 @@ int ramcrc_replay_table_lookup_host(ramcrc_replay_table_host* t, const void* key
             *counts = ramcrc_lookup_counts{0, 0, 0, 0, 1};
         return RAMCRC_OK;
     }
-    struct Rd {
-        const uint8_t* pay;
-        uint32_t u8(uint32_t o) const { return pay[o]; }
-        uint32_t u16(uint32_t o) const { return ld16(pay + o); }
-        uint32_t u32(uint32_t o) const { return ld32(pay + o); }
-        uint64_t u64(uint32_t o) const { return ld64(pay + o); }
-    };
     ramcrc_lookup_counts ct{0, 0, 0, 0, 0};
     const uint8_t* const kb = static_cast<const uint8_t*>(keys);
-    const uint64_t mask = t->slots.size() - 1;
     for (uint64_t i = 0; i < n_queries; i++) {
         ramcrc_lookup_key q;   // (no alignment rule)
         memcpy(&q, reinterpret_cast<const uint8_t*>(queries) + i * sizeof(q), sizeof(q));
-        ramcrc_lookup_result res = rl::no_result(RAMCRC_LOOKUP_BAD_KEY);
-        if (rl::bad_query(q.key_off, q.key_len, q.reserved, keys_bytes)) {
-            ct.bad++;
-        } else {
-            res.kind = RAMCRC_LOOKUP_ABSENT;
-            const uint8_t* const key = q.key_len ? kb + q.key_off : nullptr;
-            const uint64_t hash = key_hash ? key_hash[i] : ramcrc::key_hash(q.table_id, key, q.key_len);
-            uint64_t s = hash & mask;
-            for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
-                const ramcrc_replay_table_host::Slot& sl = t->slots[s];
-                if (!sl.claim)
-                    break;
-                if (sl.table_id != q.table_id || sl.key_len != q.key_len ||
-                    (q.key_len && memcmp(sl.key, key, q.key_len)))
-                    continue;
-                const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
-                const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
-                const ramcrc_seg_entry& r = bt.entries[wr];
-                const uint32_t pay = r.offset + 1 + ((r.header >> 6) & 3) + 1;
-                res.ref = ramcrc_replay_ref{wb, wr};
-                res.version = sl.version;
-                if ((sl.rank >> 48) & 1) {
-                    const rl::Value v =
-                        rl::object_value(r.length, Rd{bt.base + r.segment * bt.stride + pay});
-                    res.kind = RAMCRC_LOOKUP_OBJECT;
-                    res.segment = r.segment;
-                    res.value_off = pay + v.off;
-                    res.value_len = v.len;
-                } else {
-                    res.kind = RAMCRC_LOOKUP_TOMBSTONE;
-                }
-                break;
-            }
-            (res.kind == RAMCRC_LOOKUP_OBJECT ? ct.objects
-             : res.kind == RAMCRC_LOOKUP_TOMBSTONE ? ct.tombstones : ct.absent)++;
-        }
+        const ramcrc_lookup_result res =
+            look_one(t, kb, keys_bytes, q, key_hash ? key_hash + i : nullptr, nullptr, nullptr, nullptr);
+        (res.kind == RAMCRC_LOOKUP_OBJECT ? ct.objects
+         : res.kind == RAMCRC_LOOKUP_TOMBSTONE ? ct.tombstones
+         : res.kind == RAMCRC_LOOKUP_ABSENT ? ct.absent : ct.bad)++;
         memcpy(reinterpret_cast<uint8_t*>(results) + i * sizeof(res), &res, sizeof(res));
     }
     if (counts)
         *counts = ct;
+    return RAMCRC_OK;
+}
+
+// A multi-read's reply (the rules of read_rules.h): per query the lookup, the
+// status, the part; the loop ends at the first part that does not fit.
+int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                  const ramcrc_lookup_key* queries, uint64_t n_queries,
+                                  const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                  uint32_t flags, void* reply, uint64_t reply_cap,
+                                  uint64_t* part_off, ramcrc_lookup_result* results,
+                                  ramcrc_read_summary* summary)
+{
+    namespace rr = ramcrc_read;
+    if (!t || n_queries >= 0xFFFFFFFFull || (flags & ~RAMCRC_READ_VALUE_ONLY) ||
+        (n_queries && (!queries || !summary)) || (keys_bytes && !keys) || (reply_cap && !reply))
+        return RAMCRC_EINVAL;
+    if (!summary)
+        return RAMCRC_OK;
+    ramcrc_read_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    const uint8_t* const kb = static_cast<const uint8_t*>(keys);
+    uint8_t* const out = static_cast<uint8_t*>(reply);
+    bool open = true;   // no part has failed to fit yet
+    for (uint64_t i = 0; i < n_queries; i++) {
+        ramcrc_lookup_key q;   // (no alignment rule)
+        memcpy(&q, reinterpret_cast<const uint8_t*>(queries) + i * sizeof(q), sizeof(q));
+        rr::Rules ru = rr::no_rules();
+        if (rules) {
+            const uint8_t* const p = reinterpret_cast<const uint8_t*>(rules) + i * sizeof(*rules);
+            ru = rr::Rules{ld64(p), ld64(p + 8)};
+        }
+        const uint8_t* pay = nullptr;
+        uint32_t pay_len = 0;
+        ramcrc_look::Value v{0u, 0u};
+        const ramcrc_lookup_result res =
+            look_one(t, kb, keys_bytes, q, key_hash ? key_hash + i : nullptr, &pay, &pay_len, &v);
+        if (results)
+            memcpy(reinterpret_cast<uint8_t*>(results) + i * sizeof(res), &res, sizeof(res));
+        uint64_t version = res.version;
+        const uint32_t st = rr::status(rr::bad_rules(ru), res.kind, ru, &version);
+        rr::Data d{0u, 0u};
+        if (st == rr::kStatusOk)
+            d = rr::data_range(flags, pay_len, v);
+        const uint64_t size = rr::part_size(st, d.len);
+        uint64_t at = RAMCRC_READ_NONE;
+        if (open && size <= reply_cap - sm.reply_bytes) {
+            at = sm.reply_bytes;
+            uint64_t w[2];
+            rr::header_words(st, version, d.len, &w[0], &w[1]);
+            for (int b = 0; b < 16; b++)
+                out[at + b] = uint8_t(w[b >> 3] >> (8 * (b & 7)));
+            if (d.len)
+                memcpy(out + at + rr::kPartHeader, pay + d.off, d.len);
+            sm.returned++;
+            sm.reply_bytes += size;
+            if (st == rr::kStatusOk) {
+                sm.ok++;
+                sm.value_bytes += v.len;
+                sm.key_bytes += rr::key_bytes(pay_len, v);
+            } else {
+                (st == rr::kStatusDoesntExist ? sm.doesnt_exist
+                 : st == rr::kStatusExists ? sm.object_exists
+                 : st == rr::kStatusWrongVersion ? sm.wrong_version : sm.bad)++;
+            }
+        } else {
+            open = false;
+        }
+        if (part_off)
+            memcpy(reinterpret_cast<uint8_t*>(part_off) + i * 8, &at, 8);
+    }
+    *summary = sm;
     return RAMCRC_OK;
 }
 

@@ -120,6 +120,10 @@ def lib():
         "ramcrc_replay_table_stats_host": (i32, [vp, vp]),
         "ramcrc_replay_table_lookup_device": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp]),
         "ramcrc_replay_table_lookup_host": (i32, [vp, vp, u64, vp, u64, vp, vp, vp]),
+        "ramcrc_replay_table_read_device": (i32, [vp, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp,
+                                                  vp, vp]),
+        "ramcrc_replay_table_read_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp,
+                                                vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -499,6 +503,46 @@ class ReplayTableHost:
                                                    p(key_hash), p(results), p(counts))
         _check(rc, "ramcrc_replay_table_lookup_host")
         return results, counts[0]
+
+    def read(self, keys, queries, reply_cap, rules=None, value_only=False, key_hash=None,
+             want_results=False):
+        """A multi-read's reply (ramcrc_replay_table_read_host).  keys, queries,
+        key_hash as lookup takes them; rules: segments.REJECT_RULES_DTYPE [n]
+        (segments.read_rules packs them) or None: no rules; reply_cap: the
+        reply's limit in bytes.  Returns (reply: uint8 [reply_bytes], part_off:
+        uint64 [n], READ_NONE where a query was not returned, summary: a
+        segments.READ_SUMMARY_DTYPE scalar, results:
+        segments.LOOKUP_RESULT_DTYPE [n] or None); segments.multi_read_parts
+        splits the reply.  On a spoiled table the reply is empty, part_off and
+        results are the wrapper's zeros and summary["spoiled"] is 1."""
+        from . import segments as _seg
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        queries = np.ascontiguousarray(queries, _seg.LOOKUP_KEY_DTYPE).reshape(-1)
+        n = queries.shape[0]
+        if key_hash is not None:
+            key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+            if key_hash.size < n:
+                raise RamcrcError("ReplayTableHost.read: fewer hashes than queries")
+        if rules is not None:
+            rules = np.ascontiguousarray(rules, _seg.REJECT_RULES_DTYPE).reshape(-1)
+            if rules.size < n:
+                raise RamcrcError("ReplayTableHost.read: fewer rules than queries")
+        reply_cap = int(reply_cap)
+        # no reply is longer than its parts: 16 bytes and at most the longest
+        # payload each, so a cap beyond that changes nothing
+        longest = max([int(k[2][:, 2].max()) for k in self._keep if k[2].shape[0]], default=0)
+        room = min(reply_cap, n * (16 + longest))
+        reply = np.zeros(room, np.uint8)
+        part_off = np.zeros(n, np.uint64)
+        results = np.zeros(n, _seg.LOOKUP_RESULT_DTYPE) if want_results else None
+        summary = np.zeros(1, _seg.READ_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_read_host(
+            self._h, p(keys), keys.size, p(queries), n, p(key_hash), p(rules),
+            _seg.READ_VALUE_ONLY if value_only else 0, p(reply), room, p(part_off), p(results),
+            p(summary))
+        _check(rc, "ramcrc_replay_table_read_host")
+        return reply[:int(summary[0]["reply_bytes"])], part_off, summary[0], results
 
 
 # ---------------------------------------------------------------- device
@@ -933,6 +977,43 @@ class ReplayTable:
             int(n_queries), _ptr(key_hash), _ptr(results), _ptr(counts), _stream(stream))
         _check(rc, "ramcrc_replay_table_lookup_device")
         return results
+
+    def read(self, keys, queries, reply, summary, rules=None, value_only=False, part_off=None,
+             results=None, key_hash=None, keys_bytes=None, n_queries=None, reply_cap=None,
+             stream=None):
+        """A multi-read's reply, packed on the device
+        (ramcrc_replay_table_read_device).  keys, queries, key_hash, keys_bytes,
+        n_queries as lookup takes them; reply: uint8 CUDA out, any alignment
+        (reply_cap: its limit in bytes, default reply.numel()); summary: int64
+        CUDA [10] out (segments.READ_SUMMARY_DTYPE); rules: CUDA holding n
+        segments.REJECT_RULES_DTYPE records (16 bytes each, 8-byte aligned) or
+        None: no rules; part_off: int64 CUDA [n] out or None; results: CUDA
+        out as lookup's or None.  The reply must not overlap an added batch.
+        Asynchronous; segments.multi_read_parts splits the reply on the host."""
+        if keys_bytes is None:
+            keys_bytes = 0 if keys is None else keys.numel() * keys.element_size()
+        if n_queries is None:
+            n_queries = 0 if queries is None else queries.numel() * queries.element_size() // 24
+        if reply_cap is None:
+            reply_cap = 0 if reply is None else reply.numel() * reply.element_size()
+        nbytes = lambda x: x.numel() * x.element_size()
+        if reply_cap and (reply is None or nbytes(reply) < reply_cap):
+            raise RamcrcError("ReplayTable.read: reply is smaller than reply_cap")
+        if results is not None and nbytes(results) < 32 * n_queries:
+            raise RamcrcError("ReplayTable.read: results is smaller than the queries")
+        if part_off is not None and nbytes(part_off) < 8 * n_queries:
+            raise RamcrcError("ReplayTable.read: part_off is smaller than the queries")
+        if rules is not None and nbytes(rules) < 16 * n_queries:
+            raise RamcrcError("ReplayTable.read: fewer rules than queries")
+        if key_hash is not None and key_hash.numel() < n_queries:
+            raise RamcrcError("ReplayTable.read: fewer hashes than queries")
+        rc = lib().ramcrc_replay_table_read_device(
+            self._h, _ptr(keys) if keys_bytes else None, int(keys_bytes), _ptr(queries),
+            int(n_queries), _ptr(key_hash), _ptr(rules),
+            1 if value_only else 0, _ptr(reply) if reply_cap else None, int(reply_cap),
+            _ptr(part_off), _ptr(results), _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_read_device")
+        return reply
 
 
 # ------------------------------------------------------------ multi-GPU shard

@@ -63,6 +63,20 @@ LOOKUP_RESULT_DTYPE = np.dtype([("batch", "<u4"), ("record", "<u4"), ("version",
 LOOKUP_COUNTS_DTYPE = np.dtype([("objects", "<u8"), ("tombstones", "<u8"), ("absent", "<u8"),
                                 ("bad", "<u8"), ("spoiled", "<u8")])
 LOOKUP_ABSENT, LOOKUP_OBJECT, LOOKUP_TOMBSTONE, LOOKUP_BAD_KEY = 0, 1, 2, 3
+# ramcrc_reject_rules, ramcrc_read_summary, the flag, the not-returned mark and
+# the statuses of a part (ramcrc_replay_table_read_device / _host; src/Status.h)
+REJECT_RULES_DTYPE = np.dtype([("given_version", "<u8"), ("doesnt_exist", "u1"), ("exists", "u1"),
+                               ("version_le_given", "u1"), ("version_ne_given", "u1"),
+                               ("reserved", "<u4")])
+READ_SUMMARY_DTYPE = np.dtype([("returned", "<u8"), ("reply_bytes", "<u8"), ("ok", "<u8"),
+                               ("doesnt_exist", "<u8"), ("object_exists", "<u8"),
+                               ("wrong_version", "<u8"), ("bad", "<u8"), ("value_bytes", "<u8"),
+                               ("key_bytes", "<u8"), ("spoiled", "<u8")])
+READ_PART_DTYPE = np.dtype([("status", "<u4"), ("version", "<u8"), ("length", "<u4")])   # packed
+READ_VALUE_ONLY = 1
+READ_NONE = 0xFFFFFFFFFFFFFFFF
+STATUS_OK, STATUS_OBJECT_DOESNT_EXIST, STATUS_OBJECT_EXISTS = 0, 3, 4
+STATUS_WRONG_VERSION, STATUS_REQUEST_FORMAT_ERROR = 5, 9
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
 # (ramcrc_replay_sidelog_device / _host)
 LOG_REF_DTYPE = np.dtype([("segment", "<u4"), ("offset", "<u4")])
@@ -105,6 +119,37 @@ def lookup_queries(keys, align=1):
         parts.append(b"\0" * pad + bytes(key))
         at += pad + len(key)
     return np.frombuffer(b"".join(parts), np.uint8).copy(), q
+
+
+def read_rules(rules):
+    """REJECT_RULES_DTYPE [n] from one entry per query: None (no rule) or a
+    dict with any of given_version, doesnt_exist, exists, version_le_given,
+    version_ne_given (and reserved, which must stay 0 for a usable query)."""
+    a = np.zeros(len(rules), REJECT_RULES_DTYPE)
+    for i, r in enumerate(rules):
+        for name, v in (r or {}).items():
+            a[name][i] = int(v)
+    return a
+
+
+def multi_read_parts(reply, returned):
+    """The first `returned` parts of a multi-read's reply (bytes or a uint8
+    array) as (status, version, data bytes): a packed 16-byte READ_PART_DTYPE
+    header each, followed by `length` data bytes when the status is OK."""
+    raw = np.ascontiguousarray(reply, np.uint8).reshape(-1).tobytes() \
+        if not isinstance(reply, (bytes, bytearray)) else bytes(reply)
+    out, at = [], 0
+    for _ in range(int(returned)):
+        if at + 16 > len(raw):
+            raise ValueError("multi_read_parts: the reply ends inside a header")
+        status, version, length = (int(x) for x in np.frombuffer(raw, READ_PART_DTYPE, 1, at)[0])
+        at += 16
+        n = length if status == STATUS_OK else 0
+        if at + n > len(raw):
+            raise ValueError("multi_read_parts: the reply ends inside a part's data")
+        out.append((status, version, raw[at:at + n]))
+        at += n
+    return out
 
 
 def tablets_array(rows):
