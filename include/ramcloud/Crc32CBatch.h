@@ -429,6 +429,32 @@ class ReplayTable {
               "ramcrc_replay_table_read_device");
     }
 
+    /// MasterService::multiWrite (src/MasterService.cc:1523-1601) for nReqs
+    /// keysAndValue images, on the device: per request the lookup above, the
+    /// RejectRules, the new version as ObjectManager::writeObject chooses it
+    /// (nextVersion: segmentManager.safeVersion), then the object with its
+    /// checksum and the tombstone of the object it replaces, appended to d_out
+    /// as Segment::append writes them.  d_parts is the reply's body, nReqs
+    /// packed MultiOp::Response::WritePart; *d_outCert seals d_out.  The table
+    /// is not changed: walk d_out with *d_outCert and add() it as the next
+    /// batch.  d_summary->next_version is the safeVersion to go on with.
+    /// d_keyHash, d_rules, d_batchSegmentId, d_refs and d_old are nullable.
+    /// d_out must not overlap an input.
+    void
+    multiWrite(const void* d_data, uint64_t dataBytes, const ramcrc_write_req* d_reqs,
+               uint64_t nReqs, const uint64_t* d_keyHash, const ramcrc_reject_rules* d_rules,
+               uint64_t nextVersion, uint32_t timestamp, const uint64_t* d_batchSegmentId,
+               void* d_out, uint32_t outCapacity, ramcrc_seg_cert* d_outCert, void* d_parts,
+               ramcrc_write_ref* d_refs, ramcrc_lookup_result* d_old,
+               ramcrc_write_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_write_device(table, d_data, dataBytes, d_reqs, nReqs, d_keyHash,
+                                               d_rules, nextVersion, timestamp, d_batchSegmentId,
+                                               d_out, outCapacity, d_outCert, d_parts, d_refs,
+                                               d_old, d_summary, stream),
+              "ramcrc_replay_table_write_device");
+    }
+
   private:
     static void
     check(int rc, const char* what)

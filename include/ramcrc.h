@@ -899,6 +899,159 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
                                   uint64_t* part_off, ramcrc_lookup_result* results,
                                   ramcrc_read_summary* summary);
 
+/* A multi-write: the loop of MasterService::multiWrite
+ * (src/MasterService.cc:1523-1601) over ObjectManager::writeObject
+ * (src/ObjectManager.cc:1181-1350), against the replay table.  The call does
+ * not change the table.  It produces one sealed log segment with the new
+ * objects and the tombstones of the objects they replace; the caller walks
+ * that segment (ramcrc_segments_walk_device with *d_out_cert) and adds it as
+ * the next batch.  A new object has the old version plus one, so it wins; its
+ * tombstone carries the old version, so it beats the old object.  Reads
+ * between the write and the add see the old state.  Rules marked "ours" cover
+ * what the batch form must decide and the reference does not.
+ *
+ * Requests.  d_data holds keysAndValue images as MultiOp::Request::WritePart
+ * carries them (src/WireFormat.h:1102-1115): {u8 key count nk, nk x u16
+ * cumulative key lengths, the keys, the value}, at any byte.  Request q names
+ * data_len bytes at data_off and the table.  The host form is the definition:
+ * one loop in request order.
+ *
+ *   1. Usable.  The first key is found as ramcrc_part::parse finds an OBJ
+ *      record's with the 24-byte header in front of the data (nk = 0: the
+ *      empty key).  A request is bad -- STATUS_REQUEST_FORMAT_ERROR (9),
+ *      version 0 -- when reserved != 0, d_rules[q].reserved != 0, data_off +
+ *      data_len > data_bytes (64 bits, overflow included), 24 + data_len does
+ *      not fit 32 bits, data_len < 1, or nk > 0 and (data_len < 3 or 1 + 2 nk
+ *      + cum[0] > data_len).  Nothing of the data buffer or the table is read
+ *      for a request the first four tests reject.  So every written object is
+ *      a participant of a later add, keyed as the request was.
+ *   2. Duplicates (ours).  Among the usable requests of one call the one with
+ *      the lowest index is the only one served for its key (the table's key
+ *      identity: table id, length, bytes).  Every later one gets STATUS_RETRY
+ *      (17), version 0, and writes nothing, whatever became of the first.
+ *   3. Current version.  w is the key's winner as the lookup returns it now;
+ *      cur = w.version if w is an object, else 0 (:1218-1232).
+ *   4. rejectOperation(rules, cur) verbatim (ramcrc_replay_table_read_device);
+ *      a rejected request gets that status with version cur (:1234-1241).
+ *   5. Version (:1245-1246).  cur != 0: v = cur + 1.  cur == 0: with a =
+ *      next_version + the number of earlier requests of this call that reached
+ *      this step with cur == 0 (allocateVersion runs before the space check, so
+ *      a request that then does not fit has consumed one), ours: v = w.version
+ *      + 1 if w is a tombstone of version >= a, else v = a.  The table does not
+ *      raiseSafeVersion; without this rule a stale next_version would silently
+ *      lose the write.  uint64_t arithmetic.
+ *   6. Entries, in request order, each as Segment::append writes it (header
+ *      byte with the minimal number of length bytes, the length, the payload:
+ *      ramcrc_recovery_append_device's rules).  The object: 24 + data_len
+ *      bytes, [4, 8) the timestamp, [8, 16) v, [16, 24) the table id, then the
+ *      data unchanged, [0, 4) the finalized CRC32C of [4, end)
+ *      (Object::computeChecksum, src/Object.cc:770-819).  Directly behind it,
+ *      only when cur != 0 (:1254-1261), the tombstone: 32 + key_len bytes
+ *      (src/Object.cc:839-851): the table id, the segment id
+ *      d_batch_segment_id[w.batch] + w.segment (0 when the array is NULL), cur,
+ *      the timestamp, the checksum of [0, 28) followed by the key (:1042-1057),
+ *      the request's first key.
+ *   7. Space (:1263-1301).  A request's entries go in together or not at all.
+ *      The first served request with head + its bytes > out_capacity gets
+ *      STATUS_RETRY with version cur; ours: so does every later request that
+ *      reached this step.  Bad, duplicate and rejected requests behind the cut
+ *      keep their status.  No byte at or past the final head is written.  A
+ *      written request gets STATUS_OK and version v.
+ *
+ * Outputs.  d_parts: n_reqs packed 12-byte MultiOp::Response::WritePart, {u32
+ * status, u64 version} little-endian (src/WireFormat.h:1168-1177), the reply's
+ * body.  d_refs (nullable): where the request's entry headers lie in d_out,
+ * 0xFFFFFFFF for an entry that was not written.  d_old (nullable): bit for bit
+ * what ramcrc_replay_table_lookup_device writes for the request's first key
+ * (writeObject's removedObjBuffer, as a place); for a request that is not
+ * usable, the BAD_KEY answer.  *d_out_cert: {head, checksum},
+ * Segment::getAppendedLength's certificate of d_out, what
+ * ramcrc_segments_certify_device returns for it.  d_out starts empty: head 0
+ * and a fresh Crc32C.
+ *
+ * Summary.  Requests by outcome; tombstones; allocated (step 5's count);
+ * next_version: the larger of the input plus allocated and one past the highest
+ * version step 5's tombstone rule gave (to a request that fit or not);
+ * out_bytes; value_bytes and key_bytes (PerfStats writeObjectBytes and
+ * writeKeyBytes, :1315-1318) over the OK requests; object_bytes and
+ * tombstone_bytes, payload bytes of the written entries (TableStats'
+ * byteCount).  On a spoiled table only the summary is written, all zero with
+ * spoiled = 1, and no new refusal is raised: the lookup's rule.  n_reqs = 0
+ * writes a zeroed summary with next_version passed through and the certificate
+ * of an empty segment.
+ *
+ * RAMCRC_EINVAL before any launch: t, d_out_cert or d_summary NULL; d_reqs or
+ * d_parts NULL with n_reqs > 0; d_data NULL with data_bytes > 0; d_out NULL
+ * with out_capacity > 0; next_version = 0; n_reqs >= 2^32 - 1; misaligned d_reqs
+ * (8), d_key_hash (8), d_rules (8), d_batch_segment_id (8), d_out_cert (4),
+ * d_parts (4), d_refs (8), d_old (16) or d_summary (8).  d_data and d_out need
+ * no alignment.  d_out must not overlap any input; the call cannot check this.
+ * Data bytes are fetched as the aligned 16-byte words that hold at least one
+ * byte of a usable request.  The call reads the table and the added batches'
+ * segments and writes only its outputs: no table word changes.  Requests whose
+ * appended sizes add up past 2^64 are not supported.
+ *
+ * Scratch comes from the context: with s = the grouping table's slots (the
+ * smallest power of two >= max(64, 2 n)), 32 + 12 * ceil(n / 256) words and 8 *
+ * n + 2 * s entries.  After ramcrc_ctx_reserve(ctx, 32 + 12 * ceil(n / 256),
+ * 8 * n + 2 * s), or after any earlier call on the context that reserved as
+ * much, a write of up to n requests does not allocate.  The call is
+ * stream-ordered and asynchronous; lifetime and concurrency are the table's.
+ *
+ * Not done: multiRemove and multiIncrement (the request's `reserved` word is
+ * where an operation code would go); several output segments per call and a
+ * SEGHEADER entry; RpcResult records; index entries; STATUS_UNKNOWN_TABLET and
+ * transaction locks (the caller answers those before the call, as for the
+ * read); incrementWriteCount; any change to the table itself. */
+typedef struct ramcrc_write_req {
+    uint64_t table_id;
+    uint64_t data_off;   /* byte offset of the keysAndValue image in the data buffer */
+    uint32_t data_len;
+    uint32_t reserved;   /* must be 0 */
+} ramcrc_write_req;      /* 24 bytes */
+
+typedef struct ramcrc_write_ref {
+    uint32_t object_off;      /* offset of the object's entry header in d_out; 0xFFFFFFFF: not written */
+    uint32_t tombstone_off;   /* of the tombstone's; 0xFFFFFFFF: none */
+} ramcrc_write_ref;
+
+#define RAMCRC_STATUS_RETRY 17u                 /* src/Status.h */
+
+typedef struct ramcrc_write_summary {
+    uint64_t ok, doesnt_exist, object_exists, wrong_version, bad, retry_duplicate, retry_full;
+    uint64_t tombstones;       /* written */
+    uint64_t allocated;        /* versions taken from next_version on */
+    uint64_t next_version;     /* the caller's safeVersion after the call */
+    uint64_t out_bytes;        /* the output's head */
+    uint64_t value_bytes;      /* PerfStats writeObjectBytes of the OK requests */
+    uint64_t key_bytes;        /* writeKeyBytes: keysAndValueLength - valueLength, same requests */
+    uint64_t object_bytes;     /* payload bytes of the written objects */
+    uint64_t tombstone_bytes;  /* and of the written tombstones */
+    uint64_t spoiled;
+} ramcrc_write_summary;
+
+int ramcrc_replay_table_write_device(ramcrc_replay_table* t, const void* d_data, uint64_t data_bytes,
+                                     const ramcrc_write_req* d_reqs, uint64_t n_reqs,
+                                     const uint64_t* d_key_hash /* nullable */,
+                                     const ramcrc_reject_rules* d_rules /* nullable: no rules */,
+                                     uint64_t next_version, uint32_t timestamp,
+                                     const uint64_t* d_batch_segment_id /* nullable */,
+                                     void* d_out, uint32_t out_capacity, ramcrc_seg_cert* d_out_cert,
+                                     void* d_parts, ramcrc_write_ref* d_refs /* nullable */,
+                                     ramcrc_lookup_result* d_old /* nullable */,
+                                     ramcrc_write_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_write_host(ramcrc_replay_table_host* t, const void* data, uint64_t data_bytes,
+                                   const ramcrc_write_req* reqs, uint64_t n_reqs,
+                                   const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                   uint64_t next_version, uint32_t timestamp,
+                                   const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                   ramcrc_seg_cert* out_cert, void* parts, ramcrc_write_ref* refs,
+                                   ramcrc_lookup_result* old, ramcrc_write_summary* summary);
+
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,
  * :840-867), and where each record then lies.  The call is

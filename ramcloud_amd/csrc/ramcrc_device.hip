@@ -84,6 +84,7 @@
 #include "read_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
+#include "write_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -107,6 +108,7 @@ using ramcrc::OpTable;
 #include "dev_partition.inc"
 #include "dev_resolve.inc"
 #include "dev_replay_table.inc"
+#include "dev_write.inc"
 
 extern "C" {
 
@@ -1547,6 +1549,93 @@ int ramcrc_replay_table_read_device(ramcrc_replay_table* t, const void* d_keys, 
         hipLaunchKernelGGL(k_rtab_read_gather, grid, dim3(kPartThreads), 0, s, a, q, r);
         HIPCHK(hipGetLastError());
     }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_write_device(ramcrc_replay_table* t, const void* d_data, uint64_t data_bytes,
+                                     const ramcrc_write_req* d_reqs, uint64_t n_reqs,
+                                     const uint64_t* d_key_hash, const ramcrc_reject_rules* d_rules,
+                                     uint64_t next_version, uint32_t timestamp,
+                                     const uint64_t* d_batch_segment_id, void* d_out,
+                                     uint32_t out_capacity, ramcrc_seg_cert* d_out_cert, void* d_parts,
+                                     ramcrc_write_ref* d_refs, ramcrc_lookup_result* d_old,
+                                     ramcrc_write_summary* d_summary, void* stream)
+{
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !d_summary || !d_out_cert ||
+        (n_reqs && (!d_reqs || !d_parts)) || (data_bytes && !d_data) || (out_capacity && !d_out))
+        return RAMCRC_EINVAL;
+    const uint64_t D = reinterpret_cast<uint64_t>(d_data), O = reinterpret_cast<uint64_t>(d_out);
+    if ((reinterpret_cast<uint64_t>(d_reqs) & 7) || (reinterpret_cast<uint64_t>(d_key_hash) & 7) ||
+        (reinterpret_cast<uint64_t>(d_rules) & 7) || (reinterpret_cast<uint64_t>(d_batch_segment_id) & 7) ||
+        (reinterpret_cast<uint64_t>(d_out_cert) & 3) || (reinterpret_cast<uint64_t>(d_parts) & 3) ||
+        (reinterpret_cast<uint64_t>(d_refs) & 7) || (reinterpret_cast<uint64_t>(d_old) & 15) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || D > UINT64_MAX - data_bytes ||
+        O > UINT64_MAX - out_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: the head line, then the tile sums, in the chunk-partial buffer;
+    // the per-request words, then the grouping table, in the plan buffer
+    // (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_reqs + kPartThreads - 1) / kPartThreads;
+    const uint64_t gslots = ramcrc_res::slots_for(n_reqs);
+    int rc = reserve_locked(c, 2 * kWrHeadWords + 2 * kWrTileWords * ntiles, kWrReqWords * n_reqs + 2 * gslots);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    WrDesc w{};
+    w.data = D;
+    w.data_bytes = data_bytes;
+    w.reqs = reinterpret_cast<const uint64_t*>(d_reqs);
+    w.nq = n_reqs;
+    w.key_hash = d_key_hash;
+    w.rules = reinterpret_cast<const uint64_t*>(d_rules);
+    w.batch_seg = d_batch_segment_id;
+    w.next_version = next_version;
+    w.timestamp = timestamp;
+    w.cap = out_capacity;
+    w.out = O;
+    w.cert = d_out_cert;
+    w.parts = static_cast<uint32_t*>(d_parts);
+    w.refs = reinterpret_cast<uint2*>(d_refs);
+    w.summary = d_summary;
+    w.query = c->plan_local;
+    w.slot = w.query + 3 * n_reqs;
+    w.rec = w.slot + n_reqs;
+    w.group = reinterpret_cast<unsigned long long*>(w.rec + 4 * n_reqs);
+    w.gslots = gslots;
+    w.head = reinterpret_cast<unsigned long long*>(c->partials);
+    w.tile = reinterpret_cast<uint64_t*>(c->partials + 2 * kWrHeadWords);
+    LookDesc q{};
+    q.keys = D;
+    q.keys_bytes = data_bytes;
+    q.queries = w.query;
+    q.nq = n_reqs;
+    q.key_hash = d_key_hash;
+    q.results = reinterpret_cast<u32x4*>(d_old);
+    const dim3 grid(rtab_grid(c, n_reqs, kPartThreads));
+    HIPCHK(hipMemsetAsync(w.head, 0, (2 * kWrHeadWords + 2 * kWrTileWords * ntiles) * sizeof(uint32_t), s));
+    if (n_reqs) {
+        HIPCHK(hipMemsetAsync(w.group, 0, 2 * gslots * sizeof(uint64_t), s));
+        if (d_key_hash) {
+            hipLaunchKernelGGL(k_wr_group<true>, grid, dim3(kPartThreads), 0, s, a, w);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_wr_size<true>, grid, dim3(kPartThreads), 0, s, a, q, w);
+        } else {
+            hipLaunchKernelGGL(k_wr_group<false>, grid, dim3(kPartThreads), 0, s, a, w);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_wr_size<false>, grid, dim3(kPartThreads), 0, s, a, q, w);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_wr_scan, dim3(1), dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
+    // (at least one workgroup: an empty call still gets its certificate)
+    hipLaunchKernelGGL(k_wr_emit, grid, dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }
 

@@ -19,6 +19,8 @@
 #include <string.h>
 
 #include <new>
+#include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "gf2.h"
@@ -28,6 +30,7 @@
 #include "read_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
+#include "write_rules.h"
 
 namespace {
 
@@ -1058,6 +1061,160 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
         if (part_off)
             memcpy(reinterpret_cast<uint8_t*>(part_off) + i * 8, &at, 8);
     }
+    *summary = sm;
+    return RAMCRC_OK;
+}
+
+// A multi-write (the rules of write_rules.h): per request the first key, the
+// duplicate test, the lookup, rejectOperation, the version, then the object and
+// the tombstone of the object it replaces, appended to the one output.
+int ramcrc_replay_table_write_host(ramcrc_replay_table_host* t, const void* data, uint64_t data_bytes,
+                                   const ramcrc_write_req* reqs, uint64_t n_reqs,
+                                   const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                   uint64_t next_version, uint32_t timestamp,
+                                   const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                   ramcrc_seg_cert* out_cert, void* parts, ramcrc_write_ref* refs,
+                                   ramcrc_lookup_result* old, ramcrc_write_summary* summary)
+{
+    namespace rr = ramcrc_read;
+    namespace rw = ramcrc_write;
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !summary || !out_cert ||
+        (n_reqs && (!reqs || !parts)) || (data_bytes && !data) || (out_capacity && !out))
+        return RAMCRC_EINVAL;
+    ramcrc_write_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    struct DataRd {
+        const uint8_t* p;
+        uint32_t u8(uint32_t o) const { return p[o]; }
+        uint32_t u16(uint32_t o) const { return ld16(p + o); }
+    };
+    const uint8_t* const db = static_cast<const uint8_t*>(data);
+    uint8_t* const ob = static_cast<uint8_t*>(out);
+    std::unordered_set<std::string> seen;   // table id, then the key
+    uint32_t meta = 0xFFFFFFFFu;            // the output's running metadata checksum
+    uint64_t top = 0;                       // one past the highest version the tombstone rule gave
+    bool open = true;                       // no request has failed to fit yet
+    try {
+        for (uint64_t i = 0; i < n_reqs; i++) {
+            ramcrc_write_req q;   // (no alignment rule)
+            memcpy(&q, reinterpret_cast<const uint8_t*>(reqs) + i * sizeof(q), sizeof(q));
+            rr::Rules ru = rr::no_rules();
+            if (rules) {
+                const uint8_t* const p = reinterpret_cast<const uint8_t*>(rules) + i * sizeof(*rules);
+                ru = rr::Rules{ld64(p), ld64(p + 8)};
+            }
+            uint32_t status = rr::kStatusFormatError;
+            uint64_t version = 0;
+            ramcrc_write_ref ref{rw::kNone, rw::kNone};
+            ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
+            rw::Key key{false, 0u, 0u};
+            if (!rw::bad_request(q.data_off, q.data_len, q.reserved, rr::bad_rules(ru), data_bytes))
+                key = rw::first_key(q.data_len, DataRd{db + q.data_off});
+            if (key.ok) {
+                const uint8_t* const d = db + q.data_off;
+                ramcrc_lookup_key lk{q.table_id, q.data_off + key.off, key.len, 0u};
+                res = look_one(t, db, data_bytes, lk, key_hash ? key_hash + i : nullptr, nullptr,
+                               nullptr, nullptr);
+                std::string id(reinterpret_cast<const char*>(&q.table_id), 8);
+                id.append(reinterpret_cast<const char*>(d + key.off), key.len);
+                if (!seen.insert(id).second) {
+                    status = rw::kStatusRetry;   // a later request of a key of this call
+                    sm.retry_duplicate++;
+                } else {
+                    const bool obj = res.kind == RAMCRC_LOOKUP_OBJECT;
+                    const bool tomb = res.kind == RAMCRC_LOOKUP_TOMBSTONE;
+                    const uint64_t cur = obj ? res.version : 0;
+                    status = rr::reject(ru, cur);
+                    version = cur;
+                    if (status == rr::kStatusOk) {
+                        const uint64_t a = next_version + sm.allocated;
+                        const uint64_t v = rw::new_version(cur, tomb, res.version, a);
+                        if (cur == 0) {
+                            sm.allocated++;
+                            if (v != a && v + 1 > top)
+                                top = v + 1;
+                        }
+                        const bool with_tomb = cur != 0;
+                        const uint64_t size = rw::request_size(q.data_len, with_tomb, key.len);
+                        if (open && size <= out_capacity - sm.out_bytes) {
+                            uint8_t* e = ob + sm.out_bytes;
+                            const uint32_t olen = rw::kObjHeader + q.data_len;
+                            uint32_t nm;
+                            uint64_t m = rw::entry_meta(RAMCRC_LOG_ENTRY_TYPE_OBJ, olen, &nm);
+                            ref.object_off = uint32_t(sm.out_bytes);
+                            for (uint32_t b = 0; b < nm; b++)
+                                e[b] = uint8_t(m >> (8 * b));
+                            meta = ramcrc_update(meta, e, nm);
+                            e += nm;
+                            for (uint32_t b = 4; b < rw::kObjHeader; b++)
+                                e[b] = uint8_t(rw::obj_header_byte(b, timestamp, v, q.table_id));
+                            memcpy(e + rw::kObjHeader, d, q.data_len);
+                            const uint32_t ck = ~ramcrc_update(0xFFFFFFFFu, e + 4, olen - 4);
+                            for (int b = 0; b < 4; b++)
+                                e[b] = uint8_t(ck >> (8 * b));
+                            e += olen;
+                            if (with_tomb) {
+                                const uint32_t tlen = rw::kTombHeader + key.len;
+                                const uint64_t seg_id =
+                                    batch_segment_id ? batch_segment_id[res.ref.batch] + res.segment : 0ull;
+                                m = rw::entry_meta(RAMCRC_LOG_ENTRY_TYPE_OBJTOMB, tlen, &nm);
+                                ref.tombstone_off = uint32_t(e - ob);
+                                for (uint32_t b = 0; b < nm; b++)
+                                    e[b] = uint8_t(m >> (8 * b));
+                                meta = ramcrc_update(meta, e, nm);
+                                e += nm;
+                                for (uint32_t b = 0; b < 28; b++)
+                                    e[b] = uint8_t(rw::tomb_header_byte(b, q.table_id, seg_id, cur, timestamp));
+                                if (key.len)
+                                    memcpy(e + rw::kTombHeader, d + key.off, key.len);
+                                uint32_t tk = ramcrc_update(0xFFFFFFFFu, e, 28);
+                                tk = ~ramcrc_update(tk, e + rw::kTombHeader, key.len);
+                                for (int b = 0; b < 4; b++)
+                                    e[28 + b] = uint8_t(tk >> (8 * b));
+                                sm.tombstones++;
+                                sm.tombstone_bytes += tlen;
+                            }
+                            const uint32_t vl = rw::value_len(q.data_len, DataRd{d});
+                            sm.ok++;
+                            sm.out_bytes += size;
+                            sm.object_bytes += olen;
+                            sm.value_bytes += vl;
+                            sm.key_bytes += q.data_len - vl;
+                            version = v;
+                        } else {
+                            open = false;
+                            status = rw::kStatusRetry;   // "Must wait for cleaner"
+                            sm.retry_full++;
+                        }
+                    } else {
+                        (status == rr::kStatusDoesntExist ? sm.doesnt_exist
+                         : status == rr::kStatusExists ? sm.object_exists : sm.wrong_version)++;
+                    }
+                }
+            } else {
+                sm.bad++;
+            }
+            uint8_t* const p = static_cast<uint8_t*>(parts) + i * rw::kPartBytes;
+            memcpy(p, &status, 4);
+            memcpy(p + 4, &version, 8);
+            if (refs)
+                memcpy(reinterpret_cast<uint8_t*>(refs) + i * sizeof(ref), &ref, sizeof(ref));
+            if (old)
+                memcpy(reinterpret_cast<uint8_t*>(old) + i * sizeof(res), &res, sizeof(res));
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.next_version = next_version + sm.allocated > top ? next_version + sm.allocated : top;
+    const uint32_t head = uint32_t(sm.out_bytes);
+    uint8_t lenle[4];
+    for (int b = 0; b < 4; b++)
+        lenle[b] = uint8_t(head >> (8 * b));
+    *out_cert = ramcrc_seg_cert{head, ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
     *summary = sm;
     return RAMCRC_OK;
 }

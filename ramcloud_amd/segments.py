@@ -77,6 +77,20 @@ READ_VALUE_ONLY = 1
 READ_NONE = 0xFFFFFFFFFFFFFFFF
 STATUS_OK, STATUS_OBJECT_DOESNT_EXIST, STATUS_OBJECT_EXISTS = 0, 3, 4
 STATUS_WRONG_VERSION, STATUS_REQUEST_FORMAT_ERROR = 5, 9
+# ramcrc_write_req, ramcrc_write_ref, ramcrc_write_summary, the packed
+# MultiOp::Response::WritePart and ramcrc_seg_cert
+# (ramcrc_replay_table_write_device / _host)
+WRITE_REQ_DTYPE = np.dtype([("table_id", "<u8"), ("data_off", "<u8"), ("data_len", "<u4"),
+                            ("reserved", "<u4")])
+WRITE_PART_DTYPE = np.dtype([("status", "<u4"), ("version", "<u8")])   # packed
+WRITE_REF_DTYPE = np.dtype([("object_off", "<u4"), ("tombstone_off", "<u4")])
+WRITE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "ok", "doesnt_exist", "object_exists", "wrong_version", "bad", "retry_duplicate", "retry_full",
+    "tombstones", "allocated", "next_version", "out_bytes", "value_bytes", "key_bytes",
+    "object_bytes", "tombstone_bytes", "spoiled")])
+WRITE_REF_NONE = 0xFFFFFFFF
+CERT_DTYPE = np.dtype([("head", "<u4"), ("checksum", "<u4")])
+STATUS_RETRY = 17
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
 # (ramcrc_replay_sidelog_device / _host)
 LOG_REF_DTYPE = np.dtype([("segment", "<u4"), ("offset", "<u4")])
@@ -118,6 +132,36 @@ def lookup_queries(keys, align=1):
         q[i] = (int(table_id), at + pad, len(key), 0)
         parts.append(b"\0" * pad + bytes(key))
         at += pad + len(key)
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), q
+
+
+def keys_and_value(keys, value):
+    """The keysAndValue image of an object (MultiOp::Request::WritePart's
+    payload, Object's bytes behind its header): key count, cumulative key
+    lengths, the keys, the value.  keys: a list of up to 255 byte strings."""
+    cum, at = [], 0
+    for k in keys:
+        at += len(k)
+        cum.append(at)
+    return (bytes([len(keys)]) + np.asarray(cum, "<u2").tobytes() + b"".join(bytes(k) for k in keys)
+            + bytes(value))
+
+
+def write_requests(objects, align=1):
+    """(data buffer uint8 [data_bytes], requests WRITE_REQ_DTYPE [n]) for a list
+    of (table_id, keys, value): the keysAndValue images packed one behind the
+    other, each at a multiple of `align`.  keys: a list of byte strings, or one
+    byte string for a one-key object."""
+    q = np.zeros(len(objects), WRITE_REQ_DTYPE)
+    parts, at = [], 0
+    for i, (table_id, keys, value) in enumerate(objects):
+        if isinstance(keys, (bytes, bytearray)):
+            keys = [keys]
+        image = keys_and_value(keys, value)
+        pad = -at % align
+        q[i] = (int(table_id), at + pad, len(image), 0)
+        parts.append(b"\0" * pad + image)
+        at += pad + len(image)
     return np.frombuffer(b"".join(parts), np.uint8).copy(), q
 
 
