@@ -455,6 +455,31 @@ class ReplayTable {
               "ramcrc_replay_table_write_device");
     }
 
+    /// MasterService::multiRemove (src/MasterService.cc:1435-1505) for nReqs
+    /// keys, on the device: per request the lookup above and the RejectRules
+    /// as ObjectManager::removeObject applies them, then the tombstone of the
+    /// object it removes, appended to d_out as Segment::append writes it.
+    /// d_parts is the reply's body, nReqs packed
+    /// MultiOp::Response::RemovePart; *d_outCert seals d_out.  The table is
+    /// not changed: walk d_out with *d_outCert and add() it as the next batch.
+    /// d_summary->next_version is the safeVersion to go on with; d_old says
+    /// where each removed object lies.  d_keyHash, d_rules, d_batchSegmentId,
+    /// d_refs and d_old are nullable.  d_out must not overlap an input.
+    void
+    multiRemove(const void* d_keys, uint64_t keysBytes, const ramcrc_lookup_key* d_reqs,
+                uint64_t nReqs, const uint64_t* d_keyHash, const ramcrc_reject_rules* d_rules,
+                uint64_t nextVersion, uint32_t timestamp, const uint64_t* d_batchSegmentId,
+                void* d_out, uint32_t outCapacity, ramcrc_seg_cert* d_outCert, void* d_parts,
+                uint32_t* d_refs, ramcrc_lookup_result* d_old, ramcrc_remove_summary* d_summary,
+                void* stream = NULL)
+    {
+        check(ramcrc_replay_table_remove_device(table, d_keys, keysBytes, d_reqs, nReqs, d_keyHash,
+                                                d_rules, nextVersion, timestamp, d_batchSegmentId,
+                                                d_out, outCapacity, d_outCert, d_parts, d_refs,
+                                                d_old, d_summary, stream),
+              "ramcrc_replay_table_remove_device");
+    }
+
   private:
     static void
     check(int rc, const char* what)

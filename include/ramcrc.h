@@ -998,8 +998,9 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
  * much, a write of up to n requests does not allocate.  The call is
  * stream-ordered and asynchronous; lifetime and concurrency are the table's.
  *
- * Not done: multiRemove and multiIncrement (the request's `reserved` word is
- * where an operation code would go); several output segments per call and a
+ * Not done: multiIncrement (the request's `reserved` word is where an
+ * operation code would go; multiRemove is ramcrc_replay_table_remove_device,
+ * below); several output segments per call and a
  * SEGHEADER entry; RpcResult records; index entries; STATUS_UNKNOWN_TABLET and
  * transaction locks (the caller answers those before the call, as for the
  * read); incrementWriteCount; any change to the table itself. */
@@ -1051,6 +1052,134 @@ int ramcrc_replay_table_write_host(ramcrc_replay_table_host* t, const void* data
                                    const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
                                    ramcrc_seg_cert* out_cert, void* parts, ramcrc_write_ref* refs,
                                    ramcrc_lookup_result* old, ramcrc_write_summary* summary);
+
+/* A multi-remove: the loop of MasterService::multiRemove
+ * (src/MasterService.cc:1435-1505) over ObjectManager::removeObject
+ * (src/ObjectManager.cc:405-491), against the replay table.  The call does not
+ * change the table.  It produces one sealed log segment with the tombstones of
+ * the objects it removes; the caller walks that segment
+ * (ramcrc_segments_walk_device with *d_out_cert) and adds it as the next
+ * batch.  A tombstone carries the version of the object it removes, and at the
+ * add a tombstone beats an object of the same version, so it wins.  Reads
+ * between the remove and the add see the old state; a later write over the
+ * removed key takes its version from the write's tombstone rule.  Rules marked
+ * "ours" cover what the batch form must decide and the reference does not.
+ *
+ * Requests.  Request q is a lookup query: the table and key_len key bytes at
+ * d_keys + key_off, at any byte (ramcrc_replay_table_lookup_device; hashes,
+ * key identity and the moment of the answer are that call's).  d_rules[q],
+ * where given, are its RejectRules as the read takes them.  The host form is
+ * the definition: one loop in request order.
+ *
+ *   1. Usable.  A request is bad -- STATUS_REQUEST_FORMAT_ERROR (9), version
+ *      0 -- when the lookup would answer RAMCRC_LOOKUP_BAD_KEY for it (key_len
+ *      > 65,535, reserved != 0, key_off + key_len > keys_bytes in 64 bits,
+ *      overflow included) or d_rules[q].reserved != 0.  Nothing of the key
+ *      buffer or the table is read for it.
+ *   2. Duplicates (ours, the write's rule).  Among the usable requests of one
+ *      call the one with the lowest index is the only one served for its key
+ *      (the table's key identity: table id, length, bytes).  Every later one
+ *      gets STATUS_RETRY (17), version 0, and writes nothing, whatever became
+ *      of the first.
+ *   3. Lookup.  w is the key's winner as the lookup returns it now.  Not found
+ *      means w.kind != OBJECT: absent, or a tombstone (:430-436).  Then the
+ *      status is rejectOperation(rules, VERSION_NONEXISTENT) (:437-441):
+ *      STATUS_OBJECT_DOESNT_EXIST (3) if doesnt_exist is set, else STATUS_OK;
+ *      version 0; nothing is written.
+ *   4. Found.  cur = w.version, whatever its value: the reference tests the
+ *      entry's type, so an object of version 0 is found.  The status is
+ *      rejectOperation(rules, cur) verbatim (ramcrc_replay_table_read_device);
+ *      a rejected request gets that status with version cur (:443-447).  With
+ *      cur = 0 that is status 3, version 0, if doesnt_exist is set; otherwise
+ *      the request goes on.
+ *   5. The tombstone (:454-456), one entry as Segment::append writes it: type
+ *      LOG_ENTRY_TYPE_OBJTOMB, the minimal number of length bytes, then 32 +
+ *      key_len payload bytes (src/Object.cc:839-851): the table id, the
+ *      segment id d_batch_segment_id[w.batch] + w.segment (0 when the array is
+ *      NULL), cur, the timestamp, the CRC32C of [0, 28) followed by the key
+ *      (:1042-1057), the key's bytes from d_keys.
+ *   6. Space (:474-478).  Entries lie in request order.  The first request of
+ *      step 5 with head + its bytes > out_capacity gets STATUS_RETRY with
+ *      version cur (*outVersion is set before the append); ours: so does every
+ *      later request that reached step 5.  Requests that never reached step 5
+ *      keep their status, also behind the cut.  No byte at or past the final
+ *      head is written.  A written request gets STATUS_OK and version cur.
+ *   7. Safe version (:487).  next_version out is the larger of next_version in
+ *      and 1 + the highest cur over the written requests.  uint64_t
+ *      arithmetic: cur = 2^64 - 1 leaves it unchanged.
+ *
+ * Outputs.  d_parts: n_reqs packed 12-byte MultiOp::Response::RemovePart, {u32
+ * status, u64 version} little-endian (src/WireFormat.h:1157-1166), the reply's
+ * body.  d_refs (nullable): the offset of the request's entry header in d_out,
+ * 0xFFFFFFFF when nothing was written for it.  d_old (nullable): bit for bit
+ * what ramcrc_replay_table_lookup_device writes for the request's key
+ * (removeObject's removedObjBuffer, as a place: what a master needs to remove
+ * index entries); for a request that is not usable, the BAD_KEY answer.
+ * *d_out_cert: {head, checksum}, Segment::getAppendedLength's certificate of
+ * d_out, what ramcrc_segments_certify_device returns for it.  d_out starts
+ * empty: head 0 and a fresh Crc32C.
+ *
+ * Summary.  Requests by outcome: removed (STATUS_OK with a tombstone), ok_absent
+ * (STATUS_OK with nothing to remove), the three rejections, bad,
+ * retry_duplicate, retry_full; next_version (step 7); out_bytes;
+ * tombstone_bytes, the payload bytes of the written tombstones (TableStats'
+ * byteCount).  On a spoiled table only the summary is written, all zero with
+ * spoiled = 1, and no new refusal is raised: the lookup's rule.  n_reqs = 0
+ * writes a zeroed summary with next_version passed through and the certificate
+ * of an empty segment.
+ *
+ * RAMCRC_EINVAL before any launch: t, d_out_cert or d_summary NULL; d_reqs or
+ * d_parts NULL with n_reqs > 0; d_keys NULL with keys_bytes > 0; d_out NULL
+ * with out_capacity > 0; next_version = 0; n_reqs >= 2^32 - 1; misaligned d_reqs
+ * (8), d_key_hash (8), d_rules (8), d_batch_segment_id (8), d_out_cert (4),
+ * d_parts (4), d_refs (4), d_old (16) or d_summary (8).  d_keys and d_out need
+ * no alignment.  d_out must not overlap any input; the call cannot check this.
+ * Key bytes are fetched as the aligned 16-byte words that hold at least one
+ * byte of a usable request's key.  The call reads the table and the added
+ * batches' segments and writes only its outputs: no table word changes.
+ *
+ * Scratch comes from the context: with s = the grouping table's slots (the
+ * smallest power of two >= max(64, 2 n)), 32 + 10 * ceil(n / 256) words and 5 *
+ * n + s entries.  After ramcrc_ctx_reserve(ctx, 32 + 10 * ceil(n / 256),
+ * 5 * n + s), or after any earlier call on the context that reserved as
+ * much, a remove of up to n requests does not allocate.  The call is
+ * stream-ordered and asynchronous; lifetime and concurrency are the table's.
+ *
+ * Not done: multiIncrement; several output segments per call and a SEGHEADER
+ * entry; RpcResult records; index entries (d_old says where the removed object
+ * lies); STATUS_UNKNOWN_TABLET and transaction locks (the caller answers those
+ * before the call, as for the read); any change to the table itself. */
+typedef struct ramcrc_remove_summary {
+    uint64_t removed;        /* STATUS_OK with a tombstone written */
+    uint64_t ok_absent;      /* STATUS_OK, nothing to remove */
+    uint64_t doesnt_exist, object_exists, wrong_version, bad, retry_duplicate, retry_full;
+    uint64_t next_version;   /* the caller's safeVersion after the call */
+    uint64_t out_bytes;      /* the output's head */
+    uint64_t tombstone_bytes;/* payload bytes of the written tombstones (TableStats byteCount) */
+    uint64_t spoiled;
+} ramcrc_remove_summary;
+
+int ramcrc_replay_table_remove_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                      const ramcrc_lookup_key* d_reqs, uint64_t n_reqs,
+                                      const uint64_t* d_key_hash /* nullable */,
+                                      const ramcrc_reject_rules* d_rules /* nullable: no rules */,
+                                      uint64_t next_version, uint32_t timestamp,
+                                      const uint64_t* d_batch_segment_id /* nullable */,
+                                      void* d_out, uint32_t out_capacity, ramcrc_seg_cert* d_out_cert,
+                                      void* d_parts, uint32_t* d_refs /* nullable */,
+                                      ramcrc_lookup_result* d_old /* nullable */,
+                                      ramcrc_remove_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* reqs, uint64_t n_reqs,
+                                    const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                    uint64_t next_version, uint32_t timestamp,
+                                    const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                    ramcrc_seg_cert* out_cert, void* parts, uint32_t* refs,
+                                    ramcrc_lookup_result* old, ramcrc_remove_summary* summary);
 
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,

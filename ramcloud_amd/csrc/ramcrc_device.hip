@@ -85,6 +85,7 @@
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
+#include "remove_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -109,6 +110,7 @@ using ramcrc::OpTable;
 #include "dev_resolve.inc"
 #include "dev_replay_table.inc"
 #include "dev_write.inc"
+#include "dev_remove.inc"
 
 extern "C" {
 
@@ -1635,6 +1637,92 @@ int ramcrc_replay_table_write_device(ramcrc_replay_table* t, const void* d_data,
     HIPCHK(hipGetLastError());
     // (at least one workgroup: an empty call still gets its certificate)
     hipLaunchKernelGGL(k_wr_emit, grid, dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_remove_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                      const ramcrc_lookup_key* d_reqs, uint64_t n_reqs,
+                                      const uint64_t* d_key_hash, const ramcrc_reject_rules* d_rules,
+                                      uint64_t next_version, uint32_t timestamp,
+                                      const uint64_t* d_batch_segment_id, void* d_out,
+                                      uint32_t out_capacity, ramcrc_seg_cert* d_out_cert, void* d_parts,
+                                      uint32_t* d_refs, ramcrc_lookup_result* d_old,
+                                      ramcrc_remove_summary* d_summary, void* stream)
+{
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !d_summary || !d_out_cert ||
+        (n_reqs && (!d_reqs || !d_parts)) || (keys_bytes && !d_keys) || (out_capacity && !d_out))
+        return RAMCRC_EINVAL;
+    const uint64_t K = reinterpret_cast<uint64_t>(d_keys), O = reinterpret_cast<uint64_t>(d_out);
+    if ((reinterpret_cast<uint64_t>(d_reqs) & 7) || (reinterpret_cast<uint64_t>(d_key_hash) & 7) ||
+        (reinterpret_cast<uint64_t>(d_rules) & 7) || (reinterpret_cast<uint64_t>(d_batch_segment_id) & 7) ||
+        (reinterpret_cast<uint64_t>(d_out_cert) & 3) || (reinterpret_cast<uint64_t>(d_parts) & 3) ||
+        (reinterpret_cast<uint64_t>(d_refs) & 3) || (reinterpret_cast<uint64_t>(d_old) & 15) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || K > UINT64_MAX - keys_bytes ||
+        O > UINT64_MAX - out_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: the head line, then the tile sums, in the chunk-partial buffer;
+    // the per-request words, then the grouping table, in the plan buffer
+    // (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_reqs + kPartThreads - 1) / kPartThreads;
+    const uint64_t gslots = ramcrc_res::slots_for(n_reqs);
+    int rc = reserve_locked(c, 2 * kRmHeadWords + 2 * kRmTileWords * ntiles, kRmReqWords * n_reqs + gslots);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    RmDesc w{};
+    w.keys = K;
+    w.keys_bytes = keys_bytes;
+    w.reqs = reinterpret_cast<const uint64_t*>(d_reqs);
+    w.nq = n_reqs;
+    w.key_hash = d_key_hash;
+    w.rules = reinterpret_cast<const uint64_t*>(d_rules);
+    w.batch_seg = d_batch_segment_id;
+    w.next_version = next_version;
+    w.timestamp = timestamp;
+    w.cap = out_capacity;
+    w.out = O;
+    w.cert = d_out_cert;
+    w.parts = static_cast<uint32_t*>(d_parts);
+    w.refs = d_refs;
+    w.summary = d_summary;
+    w.hash = c->plan_local;
+    w.slot = w.hash + n_reqs;
+    w.rec = w.slot + n_reqs;
+    w.group = reinterpret_cast<unsigned long long*>(w.rec + 3 * n_reqs);
+    w.gslots = gslots;
+    w.head = reinterpret_cast<unsigned long long*>(c->partials);
+    w.tile = reinterpret_cast<uint64_t*>(c->partials + 2 * kRmHeadWords);
+    // the probe runs over the caller's own requests, with the group pass's
+    // hashes as the given ones
+    LookDesc q{};
+    q.keys = K;
+    q.keys_bytes = keys_bytes;
+    q.queries = w.reqs;
+    q.nq = n_reqs;
+    q.key_hash = w.hash;
+    q.results = reinterpret_cast<u32x4*>(d_old);
+    const dim3 grid(rtab_grid(c, n_reqs, kPartThreads));
+    HIPCHK(hipMemsetAsync(w.head, 0, (2 * kRmHeadWords + 2 * kRmTileWords * ntiles) * sizeof(uint32_t), s));
+    if (n_reqs) {
+        HIPCHK(hipMemsetAsync(w.group, 0, gslots * sizeof(uint64_t), s));
+        if (d_key_hash)
+            hipLaunchKernelGGL(k_rm_group<true>, grid, dim3(kPartThreads), 0, s, a, w);
+        else
+            hipLaunchKernelGGL(k_rm_group<false>, grid, dim3(kPartThreads), 0, s, a, w);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_rm_size, grid, dim3(kPartThreads), 0, s, a, q, w);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rm_scan, dim3(1), dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
+    // (at least one workgroup: an empty call still gets its certificate)
+    hipLaunchKernelGGL(k_rm_emit, grid, dim3(kPartThreads), 0, s, a, w);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }

@@ -31,6 +31,7 @@
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
+#include "remove_rules.h"
 
 namespace {
 
@@ -1210,6 +1211,124 @@ int ramcrc_replay_table_write_host(ramcrc_replay_table_host* t, const void* data
         return RAMCRC_ENOMEM;
     }
     sm.next_version = next_version + sm.allocated > top ? next_version + sm.allocated : top;
+    const uint32_t head = uint32_t(sm.out_bytes);
+    uint8_t lenle[4];
+    for (int b = 0; b < 4; b++)
+        lenle[b] = uint8_t(head >> (8 * b));
+    *out_cert = ramcrc_seg_cert{head, ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
+    *summary = sm;
+    return RAMCRC_OK;
+}
+
+// A multi-remove (the rules of remove_rules.h): per request the duplicate
+// test, the lookup, rejectOperation, then the tombstone of the object it
+// removes, appended to the one output.
+int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                    const ramcrc_lookup_key* reqs, uint64_t n_reqs,
+                                    const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                    uint64_t next_version, uint32_t timestamp,
+                                    const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                    ramcrc_seg_cert* out_cert, void* parts, uint32_t* refs,
+                                    ramcrc_lookup_result* old, ramcrc_remove_summary* summary)
+{
+    namespace rr = ramcrc_read;
+    namespace rw = ramcrc_write;
+    namespace rm = ramcrc_remove;
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !summary || !out_cert ||
+        (n_reqs && (!reqs || !parts)) || (keys_bytes && !keys) || (out_capacity && !out))
+        return RAMCRC_EINVAL;
+    ramcrc_remove_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    const uint8_t* const kb = static_cast<const uint8_t*>(keys);
+    uint8_t* const ob = static_cast<uint8_t*>(out);
+    std::unordered_set<std::string> seen;   // table id, then the key
+    uint32_t meta = 0xFFFFFFFFu;            // the output's running metadata checksum
+    uint64_t top = 0;                       // the highest version among the written tombstones
+    bool open = true;                       // no request has failed to fit yet
+    try {
+        for (uint64_t i = 0; i < n_reqs; i++) {
+            ramcrc_lookup_key q;   // (no alignment rule)
+            memcpy(&q, reinterpret_cast<const uint8_t*>(reqs) + i * sizeof(q), sizeof(q));
+            rr::Rules ru = rr::no_rules();
+            if (rules) {
+                const uint8_t* const p = reinterpret_cast<const uint8_t*>(rules) + i * sizeof(*rules);
+                ru = rr::Rules{ld64(p), ld64(p + 8)};
+            }
+            uint32_t status = rr::kStatusFormatError;
+            uint64_t version = 0;
+            uint32_t ref = rm::kNone;
+            ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
+            if (!rm::bad_request(q.key_off, q.key_len, q.reserved, rr::bad_rules(ru), keys_bytes)) {
+                const uint8_t* const key = kb + q.key_off;
+                res = look_one(t, kb, keys_bytes, q, key_hash ? key_hash + i : nullptr, nullptr, nullptr,
+                               nullptr);
+                std::string id(reinterpret_cast<const char*>(&q.table_id), 8);
+                if (q.key_len)
+                    id.append(reinterpret_cast<const char*>(key), q.key_len);
+                if (!seen.insert(id).second) {
+                    status = rm::kStatusRetry;   // a later request of a key of this call
+                    sm.retry_duplicate++;
+                } else {
+                    const rm::Outcome o = rm::outcome(res.kind, res.version, ru);
+                    status = o.status;
+                    version = o.version;
+                    if (o.reach) {
+                        const uint64_t size = rm::tomb_size(q.key_len);
+                        if (open && size <= out_capacity - sm.out_bytes) {
+                            uint8_t* e = ob + sm.out_bytes;
+                            const uint32_t tlen = rm::tomb_len(q.key_len);
+                            const uint64_t seg_id =
+                                batch_segment_id ? batch_segment_id[res.ref.batch] + res.segment : 0ull;
+                            uint32_t nm;
+                            const uint64_t m = rw::entry_meta(RAMCRC_LOG_ENTRY_TYPE_OBJTOMB, tlen, &nm);
+                            ref = uint32_t(sm.out_bytes);
+                            for (uint32_t b = 0; b < nm; b++)
+                                e[b] = uint8_t(m >> (8 * b));
+                            meta = ramcrc_update(meta, e, nm);
+                            e += nm;
+                            for (uint32_t b = 0; b < 28; b++)
+                                e[b] = uint8_t(rw::tomb_header_byte(b, q.table_id, seg_id, o.version, timestamp));
+                            if (q.key_len)
+                                memcpy(e + rm::kTombHeader, key, q.key_len);
+                            uint32_t tk = ramcrc_update(0xFFFFFFFFu, e, 28);
+                            tk = ~ramcrc_update(tk, e + rm::kTombHeader, q.key_len);
+                            for (int b = 0; b < 4; b++)
+                                e[28 + b] = uint8_t(tk >> (8 * b));
+                            sm.removed++;
+                            sm.out_bytes += size;
+                            sm.tombstone_bytes += tlen;
+                            if (o.version > top)
+                                top = o.version;
+                        } else {
+                            open = false;
+                            status = rm::kStatusRetry;   // "Must wait for cleaner"
+                            sm.retry_full++;
+                        }
+                    } else {
+                        (status == rr::kStatusDoesntExist ? sm.doesnt_exist
+                         : status == rr::kStatusExists ? sm.object_exists
+                         : status == rr::kStatusWrongVersion ? sm.wrong_version : sm.ok_absent)++;
+                    }
+                }
+            } else {
+                sm.bad++;
+            }
+            uint8_t* const p = static_cast<uint8_t*>(parts) + i * rm::kPartBytes;
+            memcpy(p, &status, 4);
+            memcpy(p + 4, &version, 8);
+            if (refs)
+                memcpy(reinterpret_cast<uint8_t*>(refs) + i * sizeof(ref), &ref, sizeof(ref));
+            if (old)
+                memcpy(reinterpret_cast<uint8_t*>(old) + i * sizeof(res), &res, sizeof(res));
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.next_version = rm::next_version(next_version, top);
     const uint32_t head = uint32_t(sm.out_bytes);
     uint8_t lenle[4];
     for (int b = 0; b < 4; b++)

@@ -128,6 +128,10 @@ def lib():
                                                    vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_write_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                  vp, vp, vp, vp, vp]),
+        "ramcrc_replay_table_remove_device": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
+                                                    vp, vp, vp, vp, vp, vp]),
+        "ramcrc_replay_table_remove_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
+                                                  vp, vp, vp, vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -590,6 +594,50 @@ class ReplayTableHost:
             _c.c_void_p(cert.ctypes.data), p(parts), p(refs), p(old),
             _c.c_void_p(summary.ctypes.data))
         _check(rc, "ramcrc_replay_table_write_host")
+        return out, cert[0], parts, refs, old, summary[0]
+
+    def remove(self, keys, reqs, out_capacity, next_version, timestamp=0, rules=None,
+               key_hash=None, batch_segment_id=None, want_refs=True, want_old=False):
+        """A multi-remove (ramcrc_replay_table_remove_host): the table is not
+        changed; the call returns the log segment of tombstones to walk and add
+        as the next batch.  keys: uint8 [keys_bytes]; reqs:
+        segments.LOOKUP_KEY_DTYPE [n] (segments.lookup_queries packs both);
+        rules and key_hash as read takes them; batch_segment_id: uint64 [batches]
+        or None.  Returns (out: uint8 [out_capacity], its bytes from the head on
+        untouched zeros; cert: a segments.CERT_DTYPE scalar; parts:
+        segments.REMOVE_PART_DTYPE [n]; refs: uint32 [n] or None; old:
+        segments.LOOKUP_RESULT_DTYPE [n] or None; summary: a
+        segments.REMOVE_SUMMARY_DTYPE scalar).  On a spoiled table everything but
+        the summary is the wrapper's zeros and summary["spoiled"] is 1."""
+        from . import segments as _seg
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        reqs = np.ascontiguousarray(reqs, _seg.LOOKUP_KEY_DTYPE).reshape(-1)
+        n = reqs.shape[0]
+        if key_hash is not None:
+            key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+            if key_hash.size < n:
+                raise RamcrcError("ReplayTableHost.remove: fewer hashes than requests")
+        if rules is not None:
+            rules = np.ascontiguousarray(rules, _seg.REJECT_RULES_DTYPE).reshape(-1)
+            if rules.size < n:
+                raise RamcrcError("ReplayTableHost.remove: fewer rules than requests")
+        if batch_segment_id is not None:
+            batch_segment_id = np.ascontiguousarray(batch_segment_id, np.uint64).reshape(-1)
+            if batch_segment_id.size < len(self._keep):
+                raise RamcrcError("ReplayTableHost.remove: fewer segment ids than batches")
+        out = np.zeros(int(out_capacity), np.uint8)
+        cert = np.zeros(1, _seg.CERT_DTYPE)
+        parts = np.zeros(n, _seg.REMOVE_PART_DTYPE)
+        refs = np.zeros(n, np.uint32) if want_refs else None
+        old = np.zeros(n, _seg.LOOKUP_RESULT_DTYPE) if want_old else None
+        summary = np.zeros(1, _seg.REMOVE_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_remove_host(
+            self._h, p(keys), keys.size, p(reqs), n, p(key_hash), p(rules), int(next_version),
+            int(timestamp), p(batch_segment_id), p(out), out.size,
+            _c.c_void_p(cert.ctypes.data), p(parts), p(refs), p(old),
+            _c.c_void_p(summary.ctypes.data))
+        _check(rc, "ramcrc_replay_table_remove_host")
         return out, cert[0], parts, refs, old, summary[0]
 
 
@@ -1105,6 +1153,50 @@ class ReplayTable:
             _ptr(out) if out_capacity else None, int(out_capacity), _ptr(out_cert), _ptr(parts),
             _ptr(refs), _ptr(old), _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_write_device")
+        return out
+
+    def remove(self, keys, reqs, out, out_cert, parts, summary, next_version, timestamp=0,
+               rules=None, key_hash=None, batch_segment_id=None, refs=None, old=None,
+               keys_bytes=None, n_reqs=None, out_capacity=None, stream=None):
+        """A multi-remove on the device (ramcrc_replay_table_remove_device): the
+        table is not changed; out becomes the log segment of tombstones to walk
+        (with out_cert) and add as the next batch.  keys: uint8 CUDA, any
+        alignment (keys_bytes: its length, default keys.numel()); reqs: CUDA
+        holding n segments.LOOKUP_KEY_DTYPE records (24 bytes each, 8-byte
+        aligned; n_reqs default: its bytes / 24); out: uint8 CUDA out, any
+        alignment (out_capacity default out.numel()); out_cert: int32 CUDA [2]
+        out (segments.CERT_DTYPE); parts: CUDA out, 12 bytes a request
+        (segments.REMOVE_PART_DTYPE), 4-byte aligned; summary: int64 CUDA [12]
+        out (segments.REMOVE_SUMMARY_DTYPE); rules, key_hash as read takes them;
+        batch_segment_id: int64 CUDA [batches] or None; refs: int32 CUDA [n] out
+        or None; old: CUDA out as lookup's results or None.  Asynchronous."""
+        nbytes = lambda x: x.numel() * x.element_size()
+        if keys_bytes is None:
+            keys_bytes = 0 if keys is None else nbytes(keys)
+        if n_reqs is None:
+            n_reqs = 0 if reqs is None else nbytes(reqs) // 24
+        if out_capacity is None:
+            out_capacity = 0 if out is None else nbytes(out)
+        if out_capacity and (out is None or nbytes(out) < out_capacity):
+            raise RamcrcError("ReplayTable.remove: out is smaller than out_capacity")
+        if n_reqs and (parts is None or nbytes(parts) < 12 * n_reqs):
+            raise RamcrcError("ReplayTable.remove: parts is smaller than the requests")
+        if refs is not None and nbytes(refs) < 4 * n_reqs:
+            raise RamcrcError("ReplayTable.remove: refs is smaller than the requests")
+        if old is not None and nbytes(old) < 32 * n_reqs:
+            raise RamcrcError("ReplayTable.remove: old is smaller than the requests")
+        if rules is not None and nbytes(rules) < 16 * n_reqs:
+            raise RamcrcError("ReplayTable.remove: fewer rules than requests")
+        if key_hash is not None and key_hash.numel() < n_reqs:
+            raise RamcrcError("ReplayTable.remove: fewer hashes than requests")
+        if out_cert is None or nbytes(out_cert) < 8 or summary is None or nbytes(summary) < 96:
+            raise RamcrcError("ReplayTable.remove: out_cert or summary is missing or too small")
+        rc = lib().ramcrc_replay_table_remove_device(
+            self._h, _ptr(keys) if keys_bytes else None, int(keys_bytes), _ptr(reqs), int(n_reqs),
+            _ptr(key_hash), _ptr(rules), int(next_version), int(timestamp), _ptr(batch_segment_id),
+            _ptr(out) if out_capacity else None, int(out_capacity), _ptr(out_cert), _ptr(parts),
+            _ptr(refs), _ptr(old), _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_remove_device")
         return out
 
 

@@ -89,6 +89,14 @@ WRITE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "tombstones", "allocated", "next_version", "out_bytes", "value_bytes", "key_bytes",
     "object_bytes", "tombstone_bytes", "spoiled")])
 WRITE_REF_NONE = 0xFFFFFFFF
+# the packed MultiOp::Response::RemovePart and ramcrc_remove_summary
+# (ramcrc_replay_table_remove_device / _host); a request is a LOOKUP_KEY_DTYPE
+# record and its reference one uint32, REMOVE_REF_NONE when nothing was written
+REMOVE_PART_DTYPE = np.dtype([("status", "<u4"), ("version", "<u8")])   # packed
+REMOVE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "removed", "ok_absent", "doesnt_exist", "object_exists", "wrong_version", "bad",
+    "retry_duplicate", "retry_full", "next_version", "out_bytes", "tombstone_bytes", "spoiled")])
+REMOVE_REF_NONE = 0xFFFFFFFF
 CERT_DTYPE = np.dtype([("head", "<u4"), ("checksum", "<u4")])
 STATUS_RETRY = 17
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
