@@ -480,6 +480,48 @@ class ReplayTable {
               "ramcrc_replay_table_remove_device");
     }
 
+    /// What clean(victims) would move and need now: per victim batch its
+    /// records and live objects, tombstones and entry bytes (d_usage,
+    /// nullable), and the summary whose needed_bytes and needed_records size
+    /// clean's outputs.  `victims` is a host array.  Changes nothing.
+    void
+    cleanSize(const uint32_t* victims, uint32_t nVictims, ramcrc_clean_usage* d_usage,
+              ramcrc_clean_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_clean_size_device(table, victims, nVictims, d_usage, d_summary,
+                                                    stream),
+              "ramcrc_replay_table_clean_size_device");
+    }
+
+    /// The log cleaner's relocation (LogCleaner::relocateLiveEntries,
+    /// src/LogCleaner.cc:575-722, over ObjectManager::relocateObject and
+    /// relocateTombstone) for the batches `victims` (a host array): the
+    /// records the table still references are appended to d_out, byte for
+    /// byte, and the table is re-pointed to them; everything else is dropped.
+    /// d_out becomes the next batch without a walk and without an add():
+    /// *d_outCert, *d_outStatus, d_outEntries, *d_outNEntries and d_outWork
+    /// are written as certify, the walk and add() would write them, and stay
+    /// the table's like an added batch's arrays.  d_moved[j] (nullable) is
+    /// survivor j's old {batch, record}; its new one is {the returned number,
+    /// j}.  Once `stream` has passed the call the victims' arrays are the
+    /// caller's again.  Survivors that do not fit spoil the table: size the
+    /// outputs with cleanSize().  Returns the survivor batch's number.
+    uint32_t
+    clean(const uint32_t* victims, uint32_t nVictims, void* d_out, uint32_t outCapacity,
+          ramcrc_seg_cert* d_outCert, ramcrc_seg_status* d_outStatus,
+          ramcrc_seg_entry* d_outEntries, uint64_t outEntriesCap, uint64_t* d_outNEntries,
+          uint64_t* d_outWork, ramcrc_replay_ref* d_moved, ramcrc_clean_usage* d_usage,
+          ramcrc_clean_summary* d_summary, void* stream = NULL)
+    {
+        uint32_t batch = 0;
+        check(ramcrc_replay_table_clean_device(table, victims, nVictims, d_out, outCapacity,
+                                               d_outCert, d_outStatus, d_outEntries, outEntriesCap,
+                                               d_outNEntries, d_outWork, d_moved, d_usage,
+                                               d_summary, &batch, stream),
+              "ramcrc_replay_table_clean_device");
+        return batch;
+    }
+
   private:
     static void
     check(int rc, const char* what)

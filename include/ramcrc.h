@@ -115,6 +115,11 @@ int ramcrc_ctx_destroy(ramcrc_ctx* ctx);
  * a launch may cover; max_entries = entries of the largest batch call. */
 int ramcrc_ctx_reserve(ramcrc_ctx* ctx, uint64_t max_chunks, uint64_t max_entries);
 
+/* How many times this process has allocated or grown device scratch, over all
+ * contexts.  A call "does not allocate" exactly when this count is the same
+ * before and after it; tests of the reserve formulas read it. */
+int ramcrc_debug_scratch_allocations(uint64_t* count);
+
 /* Uniform contiguous segments (the recovery-scan batch, src/BackupMasterRecovery.cc:743-809
  * per replica): segment i = d_base + i*seg_bytes, i < nseg.  d_init may be NULL.
  * Stream-ordered, asynchronous. */
@@ -1180,6 +1185,146 @@ int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* key
                                     const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
                                     ramcrc_seg_cert* out_cert, void* parts, uint32_t* refs,
                                     ramcrc_lookup_result* old, ramcrc_remove_summary* summary);
+
+/* Cleaning batches out of the table: the log cleaner's relocation step
+ * (LogCleaner::relocateLiveEntries, src/LogCleaner.cc:575-722, over
+ * ObjectManager::relocateObject, src/ObjectManager.cc:2932-2976, and
+ * relocateTombstone, :3177-3219), against the replay table.  Every write and
+ * remove produces a segment that becomes a batch, and the Lifetime rule keeps
+ * every batch's arrays; a clean copies the records of the victim batches that
+ * the table still references into one survivor segment, re-points the table
+ * to the copies, makes the survivor a batch without a walk and without an
+ * insert, and retires the victims.  Every record of an added batch knows its
+ * slot (its work word), so the call hashes nothing, probes nothing and
+ * compares no key: its cost follows the victims, never the table.
+ *
+ * 1. Victims.  victims[0 .. n_victims) are batch numbers, read on the host at
+ *    the call.  RAMCRC_EINVAL before any launch when n_victims is 0, a number
+ *    repeats, a batch was never added or was already cleaned since the last
+ *    reset, or (clean only; clean_size takes no number) max_batches numbers are
+ *    in use.  Records are taken victim by victim in the order given, within a
+ *    victim in record order.  Ours: the entries are not sorted by timestamp
+ *    (LogCleaner.cc:557-562); the caller orders the victims.
+ * 2. Live.  Record i of victim b is live exactly when it was a participant of
+ *    its add and is its key's winner now: live(b) at this moment, the slot's
+ *    pick names {b, i}.  This is relocateObject's test (:2953-2968) and the
+ *    hashReferenceExists half of relocateTombstone (:3187-3203).  Ours: a
+ *    tombstone that is not its key's winner is dropped whether or not the
+ *    segment it names still exists (the reference keeps it while
+ *    log.segmentExists, :3184, because its hash table holds no tombstones;
+ *    here the key's winner stays in the table, and a replay of what remains
+ *    gives the same answers).  A winner tombstone is always kept: the table
+ *    never deletes a key.
+ * 3. The survivor segment.  The live records are appended to d_out from head
+ *    0 as Segment::append lays entries out, each entry -- its header byte, its
+ *    length bytes, its payload -- byte for byte from the source.  No tombstone
+ *    is rewritten.  *d_out_cert = {head, checksum} is what
+ *    ramcrc_segments_certify_device returns for d_out.  No byte at or past the
+ *    head is written.
+ * 4. The survivor batch.  The call assigns the next batch number N on the
+ *    host under the handle's lock, as add does (*batch, summary.batch).
+ *    d_out_entries[j] = {0, offset, length, header} for survivor j in
+ *    increasing offset, *d_out_n_entries the number of survivors,
+ *    *d_out_status = {RAMCRC_SEG_OK, the certificate's checksum, survivors, 0}:
+ *    bit for bit what ramcrc_segment_walk_device writes for d_out (one segment
+ *    of out_capacity bytes) under *d_out_cert; d_out_work[j] is the survivor's
+ *    slot, what an add of that walk would leave.  Batch N names d_out with
+ *    n_seg = 1 and these arrays, its hashes are NULL, and its participant
+ *    counts are the moved objects and tombstones with 0 malformed.  d_moved[j]
+ *    (nullable) is survivor j's old {batch, record}; its new reference is
+ *    {N, j} (LogEntryRelocator::getNewReference).  From the call on, the
+ *    Lifetime rule covers d_out and the three arrays.
+ * 5. The table.  Afterwards no slot's pick and no slot's claim names a victim.
+ *    A pick that named victim record {b, i} names {N, j} and keeps its type
+ *    bit.  A claim that named a victim record names the key's winner after
+ *    the call, a participant of the same key in N or in a batch that stays.
+ *    Versions, the key count and the safe version do not change.  Later calls
+ *    treat N as any batch; it may be a victim of a later clean.  A clean, like
+ *    the order of adds, changes only which of several records of identical
+ *    version and type is kept.
+ * 6. Retired.  Once the stream has passed the call the victims' segments,
+ *    status arrays, record tables, hashes and work arrays are the caller's
+ *    again.  live on a cleaned batch returns RAMCRC_EINVAL; its number is not
+ *    given out again until reset; stats.batches counts numbers given out.
+ * 7. Space (ours).  The survivors fit when needed_bytes <= out_capacity and
+ *    needed_records <= out_entries_cap.  If not, nothing is moved, no slot
+ *    word changes, and the table is spoiled as by an add past key_cap (the
+ *    host has retired the victims already): the summary is {spoiled = 1,
+ *    needed_bytes, needed_records, every other field 0}; d_usage is written;
+ *    the certificate, status and count are not.  The sum of the victims'
+ *    certificate lengths always suffices as out_capacity, the sum of their
+ *    record counts as out_entries_cap; clean_size gives the exact figures.
+ * 8. clean_size writes the d_usage and the summary that clean would write
+ *    for these victims now, with out_bytes = needed_bytes and batch = 0, and
+ *    changes nothing: no table word, no number, nothing retired.  It runs
+ *    clean's own first kernels.
+ * 9. On a spoiled table only the summary is written, zero with spoiled = 1,
+ *    and no new refusal is raised; clean still takes its number and retires
+ *    its victims on the host.
+ * 10. Arguments.  RAMCRC_EINVAL before any launch for NULL t, victims or
+ *    d_summary; for clean, NULL d_out_cert, d_out_status, d_out_n_entries, or
+ *    d_out_entries / d_out_work with out_entries_cap > 0; d_out NULL with
+ *    out_capacity > 0; d_out not 16-byte aligned; out_capacity not a multiple
+ *    of 16 (it becomes a batch's stride); out_entries_cap >= 2^32; misaligned
+ *    structures (8 for 64-bit fields, 16 for d_out_entries, 4 for the
+ *    certificate and status).  The outputs must not overlap any batch of the
+ *    table; the call cannot check this.
+ * 11. Stream-ordered, asynchronous, serialised by the handle like add.
+ *    Scratch comes from the context: with T the sum over the victims of
+ *    ceil(entries_cap / 256), after ramcrc_ctx_reserve(ctx, 2 * (n_victims +
+ *    16 + 16 * T), 0) neither call allocates.
+ *
+ * Not done: relocation of RpcResult and transaction records (relocate's other
+ * cases, src/ObjectManager.cc:2426) -- they count as dropped_other, and a
+ * master that needs them keeps them itself --; TableStats decrements; several
+ * survivor segments per call; choosing victims (CleanableSegmentManager);
+ * dropping a tombstone's key from the table; recycling batch numbers. */
+typedef struct ramcrc_clean_usage {      /* one per victim, in the order given; 32 bytes */
+    uint64_t records;                    /* min(*n_entries, entries_cap) of that batch */
+    uint64_t live_objects, live_tombstones;
+    uint64_t live_bytes;                 /* entry bytes of its live records: header byte, length bytes, payload */
+} ramcrc_clean_usage;
+
+typedef struct ramcrc_clean_summary {
+    uint64_t victims, records;           /* batches given; their records read */
+    uint64_t moved_objects, moved_tombstones;
+    uint64_t object_bytes, tombstone_bytes;      /* payload bytes of the moved records */
+    uint64_t dropped_objects, dropped_tombstones;/* participants that are not their key's winner */
+    uint64_t dropped_other;              /* records that never took part: other types, malformed,
+                                            records of a segment whose status lacks RAMCRC_SEG_OK */
+    uint64_t needed_bytes, needed_records;       /* what the survivors need: sum of live_bytes, live records */
+    uint64_t out_bytes;                  /* the output's head (= needed_bytes when it fit) */
+    uint64_t batch;                      /* the survivor batch's number */
+    uint64_t spoiled;
+} ramcrc_clean_summary;
+
+int ramcrc_replay_table_clean_size_device(ramcrc_replay_table* t, const uint32_t* victims /* host */,
+                                          uint32_t n_victims, ramcrc_clean_usage* d_usage /* nullable */,
+                                          ramcrc_clean_summary* d_summary, void* stream);
+
+int ramcrc_replay_table_clean_device(ramcrc_replay_table* t, const uint32_t* victims /* host */,
+                                     uint32_t n_victims, void* d_out, uint32_t out_capacity,
+                                     ramcrc_seg_cert* d_out_cert, ramcrc_seg_status* d_out_status,
+                                     ramcrc_seg_entry* d_out_entries, uint64_t out_entries_cap,
+                                     uint64_t* d_out_n_entries, uint64_t* d_out_work,
+                                     ramcrc_replay_ref* d_moved /* nullable */,
+                                     ramcrc_clean_usage* d_usage /* nullable */,
+                                     ramcrc_clean_summary* d_summary, uint32_t* batch /* host, nullable */,
+                                     void* stream);
+
+/* The same on the host table, single-threaded: host pointers, no alignment
+ * rules, the same bytes.  Where the device form spoils the table (rule 7) the
+ * host form does too and returns RAMCRC_EINVAL after writing the summary. */
+int ramcrc_replay_table_clean_size_host(ramcrc_replay_table_host* t, const uint32_t* victims,
+                                        uint32_t n_victims, ramcrc_clean_usage* usage,
+                                        ramcrc_clean_summary* summary);
+int ramcrc_replay_table_clean_host(ramcrc_replay_table_host* t, const uint32_t* victims,
+                                   uint32_t n_victims, void* out, uint32_t out_capacity,
+                                   ramcrc_seg_cert* out_cert, ramcrc_seg_status* out_status,
+                                   ramcrc_seg_entry* out_entries, uint64_t out_entries_cap,
+                                   uint64_t* out_n_entries, uint64_t* out_work,
+                                   ramcrc_replay_ref* moved, ramcrc_clean_usage* usage,
+                                   ramcrc_clean_summary* summary, uint32_t* batch);
 
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,

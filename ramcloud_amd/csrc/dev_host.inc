@@ -105,10 +105,13 @@ struct ramcrc_ctx {
 
 namespace {
 
+std::atomic<uint64_t> g_scratch_allocations{0};   // ramcrc_debug_scratch_allocations
+
 int grow_device(void** p, uint64_t* cap, uint64_t need_elems, size_t elem)
 {
     if (*cap >= need_elems && *p)
         return RAMCRC_OK;
+    g_scratch_allocations.fetch_add(1, std::memory_order_relaxed);
     uint64_t n = need_elems < 1024 ? 1024 : need_elems;
     if (*p) {
         HIPCHK(hipDeviceSynchronize());

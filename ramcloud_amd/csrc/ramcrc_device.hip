@@ -69,6 +69,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <atomic>
 #include <mutex>
 #include <new>
 #include <utility>
@@ -86,6 +87,7 @@
 #include "sidelog_rules.h"
 #include "write_rules.h"
 #include "remove_rules.h"
+#include "clean_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -111,6 +113,7 @@ using ramcrc::OpTable;
 #include "dev_replay_table.inc"
 #include "dev_write.inc"
 #include "dev_remove.inc"
+#include "dev_clean.inc"
 
 extern "C" {
 
@@ -266,6 +269,14 @@ int ramcrc_ctx_reserve(ramcrc_ctx* c, uint64_t max_chunks, uint64_t max_entries)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceGuard g(c->device);
     return reserve_locked(c, max_chunks, max_entries);
+}
+
+int ramcrc_debug_scratch_allocations(uint64_t* count)
+{
+    if (!count)
+        return RAMCRC_EINVAL;
+    *count = g_scratch_allocations.load(std::memory_order_relaxed);
+    return RAMCRC_OK;
 }
 
 int ramcrc_ctx_set_option(ramcrc_ctx* c, int option, int64_t value)
@@ -1245,7 +1256,8 @@ struct ramcrc_replay_table {
     unsigned long long* mem = nullptr;   // the head, the descriptors, the batches' counters, the slots
     uint64_t key_cap = 0, nslots = 0;
     uint32_t max_batches = 0;
-    std::vector<uint64_t> ecap;   // entries_cap of every batch added since the last reset
+    std::vector<uint64_t> ecap;   // entries_cap of every batch numbered since the last reset
+    std::vector<uint8_t> retired; // 1: the batch was cleaned out (ramcrc_replay_table_clean_device)
 };
 
 namespace {
@@ -1331,6 +1343,7 @@ int ramcrc_replay_table_reset(ramcrc_replay_table* t, void* stream)
                        dim3(kPartThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
     HIPCHK(hipGetLastError());
     t->ecap.clear();
+    t->retired.clear();
     return RAMCRC_OK;
 }
 
@@ -1371,6 +1384,7 @@ int ramcrc_replay_table_add_device(ramcrc_replay_table* t, const void* d_base, u
     hipLaunchKernelGGL(k_rtab_open, dim3(1), dim3(kWaveSize), 0, s, a);
     HIPCHK(hipGetLastError());
     t->ecap.push_back(entries_cap);
+    t->retired.push_back(0);
     if (batch)
         *batch = a.batch;
     const dim3 grid(rtab_grid(c, entries_cap, kPartThreads));
@@ -1392,7 +1406,7 @@ int ramcrc_replay_table_live_device(ramcrc_replay_table* t, uint32_t batch,
     if (!t || !d_n_live || !d_counts || live_cap >= 0xFFFFFFFFull || (live_cap && !d_live))
         return RAMCRC_EINVAL;
     std::lock_guard<std::mutex> lt(t->mu);
-    if (batch >= t->ecap.size())
+    if (batch >= t->ecap.size() || t->retired[batch])
         return RAMCRC_EINVAL;
     ramcrc_ctx* c = t->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
@@ -1725,6 +1739,160 @@ int ramcrc_replay_table_remove_device(ramcrc_replay_table* t, const void* d_keys
     hipLaunchKernelGGL(k_rm_emit, grid, dim3(kPartThreads), 0, s, a, w);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
+}
+
+namespace {
+// clean and clean_size: out == nullptr is the size form.
+struct CleanOut {
+    void* out;
+    uint32_t cap;
+    ramcrc_seg_cert* cert;
+    ramcrc_seg_status* status;
+    ramcrc_seg_entry* entries;
+    uint64_t ecap;
+    uint64_t* n_entries;
+    uint64_t* work;
+    ramcrc_replay_ref* moved;
+    uint32_t* batch;
+};
+
+int clean_impl(ramcrc_replay_table* t, const uint32_t* victims, uint32_t n_victims, const CleanOut* o,
+               ramcrc_clean_usage* d_usage, ramcrc_clean_summary* d_summary, void* stream)
+{
+    if (!t || !victims || !d_summary || n_victims == 0)
+        return RAMCRC_EINVAL;
+    if ((reinterpret_cast<uint64_t>(d_usage) & 7) || (reinterpret_cast<uint64_t>(d_summary) & 7))
+        return RAMCRC_EINVAL;
+    if (o) {
+        const uint64_t O = reinterpret_cast<uint64_t>(o->out);
+        if (!o->cert || !o->status || !o->n_entries || (o->ecap && (!o->entries || !o->work)) ||
+            (o->cap && !o->out) || (O & 15) || (o->cap & 15) || o->ecap >= 0x100000000ull ||
+            O > UINT64_MAX - o->cap || (reinterpret_cast<uint64_t>(o->cert) & 3) ||
+            (reinterpret_cast<uint64_t>(o->status) & 3) || (reinterpret_cast<uint64_t>(o->entries) & 15) ||
+            (reinterpret_cast<uint64_t>(o->n_entries) & 7) || (reinterpret_cast<uint64_t>(o->work) & 7) ||
+            (reinterpret_cast<uint64_t>(o->moved) & 7))
+            return RAMCRC_EINVAL;
+    }
+    std::lock_guard<std::mutex> lt(t->mu);
+    if (o && t->ecap.size() >= t->max_batches)
+        return RAMCRC_EINVAL;
+    // the victims: numbered, not cleaned, none twice; their tiles
+    std::vector<uint64_t> vic;
+    uint64_t ntiles = 0;
+    try {
+        std::vector<uint8_t> seen(t->ecap.size(), 0);
+        vic.reserve(uint64_t(n_victims) + 1);
+        for (uint32_t v = 0; v < n_victims; v++) {
+            const uint32_t b = victims[v];
+            if (b >= t->ecap.size() || t->retired[b] || seen[b])
+                return RAMCRC_EINVAL;
+            seen[b] = 1;
+            vic.push_back((uint64_t(b) << 48) | ntiles);
+            ntiles += (t->ecap[b] + kPartThreads - 1) / kPartThreads;
+        }
+        vic.push_back(ntiles);
+        if (o) {
+            t->ecap.reserve(t->ecap.size() + 1);
+            t->retired.reserve(t->retired.size() + 1);
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch, in the chunk-partial buffer: the victim list, then a line per
+    // tile (ramcrc.h states this size)
+    const uint64_t vic_words = (uint64_t(n_victims) + 1 + 15) & ~15ull;
+    int rc = reserve_locked(c, 2 * (uint64_t(n_victims) + 16 + kClTileWords * ntiles), 0);
+    if (rc)
+        return rc;
+    RtabDesc a = rtab_desc(t);
+    ClDesc d{};
+    d.nvic = n_victims;
+    d.ntiles = ntiles;
+    uint64_t* const d_vic = reinterpret_cast<uint64_t*>(c->partials);
+    d.vic = d_vic;
+    d.tile = d_vic + vic_words;
+    d.size_only = o ? 0u : 1u;
+    d.usage = d_usage;
+    d.summary = d_summary;
+    // the list travels in the kernels' arguments: the call stays capturable
+    // and no host memory has to outlive it
+    for (uint64_t f = 0; f < vic.size(); f += kClOpenMax) {
+        ClOpen op;
+        op.vic = d_vic;
+        op.first = f;
+        op.n = uint32_t(vic.size() - f < kClOpenMax ? vic.size() - f : kClOpenMax);
+        memcpy(op.w, vic.data() + f, op.n * sizeof(uint64_t));
+        hipLaunchKernelGGL(k_clean_open, dim3(1), dim3(kClOpenMax), 0, s, op);
+        HIPCHK(hipGetLastError());
+    }
+    if (o) {
+        d.survivor = a.batch = uint32_t(t->ecap.size());
+        d.out = reinterpret_cast<uint64_t>(o->out);
+        d.cap = o->cap;
+        d.ecap = o->ecap;
+        d.cert = o->cert;
+        d.status = o->status;
+        d.entries = reinterpret_cast<u32x4*>(o->entries);
+        d.n_entries = o->n_entries;
+        d.work = o->work;
+        d.moved = reinterpret_cast<uint2*>(o->moved);
+        // the survivor is a batch of the table from here on
+        a.open.base = d.out;
+        a.open.stride = o->cap;
+        a.open.nseg = 1;
+        a.open.status = o->status;
+        a.open.entries = reinterpret_cast<const u32x4*>(o->entries);
+        a.open.n_entries = o->n_entries;
+        a.open.ecap = o->ecap;
+        a.open.key_hash = nullptr;   // nothing reads a batch's hashes after its insert
+        a.open.work = o->work;
+        hipLaunchKernelGGL(k_rtab_open, dim3(1), dim3(kWaveSize), 0, s, a);
+        HIPCHK(hipGetLastError());
+        // the number is taken and the victims are retired whatever the device finds
+        t->ecap.push_back(o->ecap);
+        t->retired.push_back(0);
+        for (uint32_t v = 0; v < n_victims; v++)
+            t->retired[victims[v]] = 1;
+        if (o->batch)
+            *o->batch = d.survivor;
+    }
+    const dim3 grid(rtab_grid(c, ntiles * kPartThreads, kPartThreads));
+    hipLaunchKernelGGL(k_clean_mark, grid, dim3(kPartThreads), 0, s, a, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(kPartThreads), 0, s, a, d);
+    HIPCHK(hipGetLastError());
+    if (o) {
+        hipLaunchKernelGGL(k_clean_move, grid, dim3(kPartThreads), 0, s, a, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_clean_claims, grid, dim3(kPartThreads), 0, s, a, d);
+        HIPCHK(hipGetLastError());
+    }
+    return RAMCRC_OK;
+}
+}  // namespace
+
+int ramcrc_replay_table_clean_size_device(ramcrc_replay_table* t, const uint32_t* victims,
+                                          uint32_t n_victims, ramcrc_clean_usage* d_usage,
+                                          ramcrc_clean_summary* d_summary, void* stream)
+{
+    return clean_impl(t, victims, n_victims, nullptr, d_usage, d_summary, stream);
+}
+
+int ramcrc_replay_table_clean_device(ramcrc_replay_table* t, const uint32_t* victims, uint32_t n_victims,
+                                     void* d_out, uint32_t out_capacity, ramcrc_seg_cert* d_out_cert,
+                                     ramcrc_seg_status* d_out_status, ramcrc_seg_entry* d_out_entries,
+                                     uint64_t out_entries_cap, uint64_t* d_out_n_entries,
+                                     uint64_t* d_out_work, ramcrc_replay_ref* d_moved,
+                                     ramcrc_clean_usage* d_usage, ramcrc_clean_summary* d_summary,
+                                     uint32_t* batch, void* stream)
+{
+    const CleanOut o{d_out, out_capacity, d_out_cert, d_out_status, d_out_entries, out_entries_cap,
+                     d_out_n_entries, d_out_work, d_moved, batch};
+    return clean_impl(t, victims, n_victims, &o, d_usage, d_summary, stream);
 }
 
 int ramcrc_verify_objects_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,

@@ -32,6 +32,7 @@
 #include "sidelog_rules.h"
 #include "write_rules.h"
 #include "remove_rules.h"
+#include "clean_rules.h"
 
 namespace {
 
@@ -694,6 +695,7 @@ struct ramcrc_replay_table_host {
         const uint8_t* base;   // the batch's segments and record table: a lookup reads its winner's record
         uint64_t stride;
         const ramcrc_seg_entry* entries;
+        bool retired;          // cleaned out (ramcrc_replay_table_clean_host): nothing of it is read
     };
     uint64_t key_cap = 0, keys = 0, safe_version = 0;
     uint32_t max_batches = 0;
@@ -762,7 +764,7 @@ int ramcrc_replay_table_add_host(ramcrc_replay_table_host* t, const void* base, 
     const uint64_t bno = t->batches.size();
     try {
         t->batches.push_back(ramcrc_replay_table_host::Batch{
-            work, n_entries, 0, 0, 0, static_cast<const uint8_t*>(base), seg_stride, entries});
+            work, n_entries, 0, 0, 0, static_cast<const uint8_t*>(base), seg_stride, entries, false});
     } catch (...) {
         return RAMCRC_ENOMEM;
     }
@@ -852,7 +854,7 @@ int ramcrc_replay_table_live_host(ramcrc_replay_table_host* t, uint32_t batch,
                                   uint64_t live_cap, uint64_t* n_live, ramcrc_resolve_counts* counts)
 {
     if (!t || !n_live || !counts || live_cap >= 0xFFFFFFFFull || (live_cap && !live) ||
-        batch >= t->batches.size())
+        batch >= t->batches.size() || t->batches[batch].retired)
         return RAMCRC_EINVAL;
     *n_live = 0;
     *counts = ramcrc_resolve_counts{0, 0, 0, 0, 0, 0};
@@ -1336,6 +1338,192 @@ int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* key
     *out_cert = ramcrc_seg_cert{head, ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
     *summary = sm;
     return RAMCRC_OK;
+}
+
+// Cleaning (the rules of clean_rules.h): a pass over the victims' records for
+// the usage and the summary; then, for clean, the copy of the live entries
+// with their rows, the winners' new ranks, and the claims that named a victim.
+namespace {
+int clean_host(ramcrc_replay_table_host* t, const uint32_t* victims, uint32_t n_victims, bool size_only,
+               void* out, uint32_t out_capacity, ramcrc_seg_cert* out_cert, ramcrc_seg_status* out_status,
+               ramcrc_seg_entry* out_entries, uint64_t out_entries_cap, uint64_t* out_n_entries,
+               uint64_t* out_work, ramcrc_replay_ref* moved, ramcrc_clean_usage* usage,
+               ramcrc_clean_summary* summary, uint32_t* batch)
+{
+    namespace cl = ramcrc_clean;
+    typedef ramcrc_replay_table_host::Batch Batch;
+    if (!t || !victims || !summary || n_victims == 0)
+        return RAMCRC_EINVAL;
+    if (!size_only &&
+        (!out_cert || !out_status || !out_n_entries || (out_entries_cap && (!out_entries || !out_work)) ||
+         (out_capacity && !out) || (out_capacity & 15) || out_entries_cap >= 0x100000000ull ||
+         t->batches.size() >= t->max_batches))
+        return RAMCRC_EINVAL;
+    try {
+        std::vector<uint8_t> seen(t->batches.size(), 0);
+        for (uint32_t v = 0; v < n_victims; v++) {
+            const uint32_t b = victims[v];
+            if (b >= t->batches.size() || t->batches[b].retired || seen[b])
+                return RAMCRC_EINVAL;
+            seen[b] = 1;
+        }
+        if (!size_only)
+            t->batches.reserve(t->batches.size() + 1);
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    ramcrc_clean_summary sm{};
+    const uint32_t N = uint32_t(t->batches.size());
+    if (!size_only) {
+        // the number is taken and the victims are retired whatever follows
+        for (uint32_t v = 0; v < n_victims; v++)
+            t->batches[victims[v]].retired = true;
+        t->batches.push_back(Batch{out_work, 0, 0, 0, 0, static_cast<const uint8_t*>(out), out_capacity,
+                                   out_entries, false});
+        if (batch)
+            *batch = N;
+    }
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    for (uint32_t v = 0; v < n_victims; v++) {
+        const uint32_t b = victims[v];
+        const Batch& bt = t->batches[b];
+        ramcrc_clean_usage u{bt.n, 0, 0, 0};
+        for (uint64_t i = 0; i < bt.n; i++) {
+            const ramcrc_seg_entry& r = bt.entries[i];
+            const uint64_t w = bt.work[i];
+            const uint64_t rank = w != cl::kNoSlot ? t->slots[w].rank : 0ull;
+            switch (cl::classify(w, rank, b, i, r.header)) {
+            case cl::kLiveObject:
+                u.live_objects++;
+                u.live_bytes += cl::entry_bytes(r.header, r.length);
+                sm.object_bytes += r.length;
+                break;
+            case cl::kLiveTombstone:
+                u.live_tombstones++;
+                u.live_bytes += cl::entry_bytes(r.header, r.length);
+                sm.tombstone_bytes += r.length;
+                break;
+            case cl::kDroppedObject:
+                sm.dropped_objects++;
+                break;
+            case cl::kDroppedTombstone:
+                sm.dropped_tombstones++;
+                break;
+            default:
+                sm.dropped_other++;
+            }
+        }
+        sm.records += u.records;
+        sm.moved_objects += u.live_objects;
+        sm.moved_tombstones += u.live_tombstones;
+        sm.needed_bytes += u.live_bytes;
+        if (usage)
+            memcpy(reinterpret_cast<uint8_t*>(usage) + v * sizeof(u), &u, sizeof(u));
+    }
+    sm.victims = n_victims;
+    sm.needed_records = sm.moved_objects + sm.moved_tombstones;
+    sm.out_bytes = sm.needed_bytes;
+    if (size_only) {
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    if (!cl::fits(sm.needed_bytes, sm.needed_records, out_capacity, out_entries_cap)) {
+        ramcrc_clean_summary no{};
+        no.needed_bytes = sm.needed_bytes;
+        no.needed_records = sm.needed_records;
+        no.spoiled = 1;
+        *summary = no;
+        t->spoiled = true;
+        return RAMCRC_EINVAL;
+    }
+    sm.batch = N;
+    uint8_t* const ob = static_cast<uint8_t*>(out);
+    uint32_t meta = 0xFFFFFFFFu;   // the survivor's running metadata checksum
+    uint64_t head = 0, j = 0;
+    for (uint32_t v = 0; v < n_victims; v++) {
+        const uint32_t b = victims[v];
+        const Batch& bt = t->batches[b];
+        for (uint64_t i = 0; i < bt.n; i++) {
+            const ramcrc_seg_entry& r = bt.entries[i];
+            const uint64_t w = bt.work[i];
+            if (w == cl::kNoSlot || !cl::live(w, t->slots[w].rank, b, i))
+                continue;
+            const uint64_t size = cl::entry_bytes(r.header, r.length);
+            const uint8_t* const src = bt.base + r.segment * bt.stride + r.offset;
+            memcpy(ob + head, src, size);
+            meta = ramcrc_update(meta, src, cl::meta_bytes(r.header));
+            const ramcrc_seg_entry row{0u, uint32_t(head), r.length, r.header};
+            memcpy(reinterpret_cast<uint8_t*>(out_entries) + j * sizeof(row), &row, sizeof(row));
+            memcpy(reinterpret_cast<uint8_t*>(out_work) + j * sizeof(w), &w, sizeof(w));
+            if (moved) {
+                const ramcrc_replay_ref old{b, uint32_t(i)};
+                memcpy(reinterpret_cast<uint8_t*>(moved) + j * sizeof(old), &old, sizeof(old));
+            }
+            t->slots[w].rank =
+                cl::rank_of((r.header & 0x3f) == RAMCRC_LOG_ENTRY_TYPE_OBJ, N, j);
+            head += size;
+            j++;
+        }
+    }
+    Batch& nb = t->batches[N];
+    nb.n = j;
+    nb.objects = sm.moved_objects;
+    nb.tombstones = sm.moved_tombstones;
+    // every winner names a batch that stays: the claims that named a victim
+    for (uint32_t v = 0; v < n_victims; v++) {
+        const uint32_t b = victims[v];
+        const Batch& bt = t->batches[b];
+        for (uint64_t i = 0; i < bt.n; i++) {
+            const uint64_t w = bt.work[i];
+            if (w == cl::kNoSlot || t->slots[w].claim != cl::claim_of(b, i))
+                continue;
+            ramcrc_replay_table_host::Slot& sl = t->slots[w];
+            sl.claim = cl::claim_after(sl.rank);
+            const Batch& wb = t->batches[cl::claim_batch(sl.claim)];
+            ramcrc_seg_entry r;   // (the survivor's table has no alignment rule)
+            memcpy(&r, reinterpret_cast<const uint8_t*>(wb.entries) + cl::claim_record(sl.claim) * sizeof(r),
+                   sizeof(r));
+            const uint64_t pay = uint64_t(r.offset) + 1 + ((r.header >> 6) & 3) + 1;
+            const LookRd rd{wb.base + r.segment * wb.stride + pay};
+            const ramcrc_part::Parsed p = ramcrc_part::parse(r.header & 0x3f, r.length, true, rd);
+            sl.key = rd.pay + p.key_off;   // the same key, in a batch that stays
+        }
+    }
+    uint8_t lenle[4];
+    for (int k = 0; k < 4; k++)
+        lenle[k] = uint8_t(uint32_t(head) >> (8 * k));
+    const ramcrc_seg_cert cert{uint32_t(head), ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
+    const ramcrc_seg_status st{RAMCRC_SEG_OK, cert.checksum, uint32_t(j), 0u};
+    memcpy(out_cert, &cert, sizeof(cert));
+    memcpy(out_status, &st, sizeof(st));
+    memcpy(out_n_entries, &j, sizeof(j));
+    *summary = sm;
+    return RAMCRC_OK;
+}
+}  // namespace
+
+int ramcrc_replay_table_clean_size_host(ramcrc_replay_table_host* t, const uint32_t* victims,
+                                        uint32_t n_victims, ramcrc_clean_usage* usage,
+                                        ramcrc_clean_summary* summary)
+{
+    return clean_host(t, victims, n_victims, true, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr,
+                      nullptr, nullptr, usage, summary, nullptr);
+}
+
+int ramcrc_replay_table_clean_host(ramcrc_replay_table_host* t, const uint32_t* victims,
+                                   uint32_t n_victims, void* out, uint32_t out_capacity,
+                                   ramcrc_seg_cert* out_cert, ramcrc_seg_status* out_status,
+                                   ramcrc_seg_entry* out_entries, uint64_t out_entries_cap,
+                                   uint64_t* out_n_entries, uint64_t* out_work,
+                                   ramcrc_replay_ref* moved, ramcrc_clean_usage* usage,
+                                   ramcrc_clean_summary* summary, uint32_t* batch)
+{
+    return clean_host(t, victims, n_victims, false, out, out_capacity, out_cert, out_status, out_entries,
+                      out_entries_cap, out_n_entries, out_work, moved, usage, summary, batch);
 }
 
 }  // extern "C"

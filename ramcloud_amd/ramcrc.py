@@ -79,6 +79,7 @@ def lib():
         "ramcrc_ctx_create": (i32, [i32, _c.POINTER(vp)]),
         "ramcrc_ctx_destroy": (i32, [vp]),
         "ramcrc_ctx_reserve": (i32, [vp, u64, u64]),
+        "ramcrc_debug_scratch_allocations": (i32, [_c.POINTER(u64)]),
         "ramcrc_segments_device": (i32, [vp, vp, u64, u64, vp, vp, u32, vp]),
         "ramcrc_batch_device": (i32, [vp, vp, vp, vp, vp, vp, u64, u32, vp]),
         "ramcrc_entries_device": (i32, [vp, vp, vp, vp, vp, vp, u64, u32, vp]),
@@ -132,6 +133,12 @@ def lib():
                                                     vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_remove_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                   vp, vp, vp, vp, vp]),
+        "ramcrc_replay_table_clean_size_device": (i32, [vp, vp, u32, vp, vp, vp]),
+        "ramcrc_replay_table_clean_device": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u64, vp, vp, vp,
+                                                   vp, vp, _c.POINTER(u32), vp]),
+        "ramcrc_replay_table_clean_size_host": (i32, [vp, vp, u32, vp, vp]),
+        "ramcrc_replay_table_clean_host": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u64, vp, vp, vp,
+                                                 vp, vp, _c.POINTER(u32)]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -250,6 +257,15 @@ def cpu_has_hw():
 
 def device_count():
     return int(lib().ramcrc_device_count())
+
+
+def scratch_allocations():
+    """How often this process has allocated or grown device scratch
+    (ramcrc_debug_scratch_allocations): unchanged across a call that does not
+    allocate."""
+    n = _c.c_uint64(0)
+    _check(lib().ramcrc_debug_scratch_allocations(_c.byref(n)), "ramcrc_debug_scratch_allocations")
+    return n.value
 
 
 def segment_fill_objects(seg, value_len, first_key=0):
@@ -467,8 +483,8 @@ class ReplayTableHost:
         segments.REPLAY_REF_DTYPE [n], live uint32 [m, 2] with m = min(needed,
         live_cap), needed, counts: a segments.RESOLVE_COUNTS_DTYPE scalar)."""
         from . import segments as _seg
-        if not 0 <= int(batch) < len(self._keep):
-            raise RamcrcError("ReplayTableHost.live: no such batch", EINVAL)
+        if not 0 <= int(batch) < len(self._keep) or self._keep[int(batch)] is None:
+            raise RamcrcError("ReplayTableHost.live: no such batch, or a cleaned one", EINVAL)
         n = self._keep[int(batch)][2].shape[0]
         cap = n if live_cap is None else int(live_cap)
         winner = np.zeros(n, _seg.REPLAY_REF_DTYPE)
@@ -538,7 +554,9 @@ class ReplayTableHost:
         reply_cap = int(reply_cap)
         # no reply is longer than its parts: 16 bytes and at most the longest
         # payload each, so a cap beyond that changes nothing
-        longest = max([int(k[2][:, 2].max()) for k in self._keep if k[2].shape[0]], default=0)
+        # (a cleaned batch keeps its number and holds nothing)
+        longest = max([int(k[2][:, 2].max()) for k in self._keep if k is not None and k[2].shape[0]],
+                      default=0)
         room = min(reply_cap, n * (16 + longest))
         reply = np.zeros(room, np.uint8)
         part_off = np.zeros(n, np.uint64)
@@ -639,6 +657,72 @@ class ReplayTableHost:
             _c.c_void_p(summary.ctypes.data))
         _check(rc, "ramcrc_replay_table_remove_host")
         return out, cert[0], parts, refs, old, summary[0]
+
+    def clean_size(self, victims):
+        """What clean(victims) would need and move now
+        (ramcrc_replay_table_clean_size_host); changes nothing.  Returns (usage:
+        segments.CLEAN_USAGE_DTYPE [n_victims], summary: a
+        segments.CLEAN_SUMMARY_DTYPE scalar)."""
+        from . import segments as _seg
+        victims = np.ascontiguousarray(victims, np.uint32).reshape(-1)
+        usage = np.zeros(victims.size, _seg.CLEAN_USAGE_DTYPE)
+        summary = np.zeros(1, _seg.CLEAN_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a.size else None
+        rc = lib().ramcrc_replay_table_clean_size_host(self._h, p(victims), victims.size, p(usage),
+                                                       _c.c_void_p(summary.ctypes.data))
+        _check(rc, "ramcrc_replay_table_clean_size_host")
+        return usage, summary[0]
+
+    def clean(self, victims, out_capacity, out_entries_cap, want_moved=True, fill=0):
+        """Clean batches out of the table (ramcrc_replay_table_clean_host): the
+        victims' live records move to one survivor segment, which becomes the
+        next batch; the victims' arrays are released.  Returns a dict: out
+        (uint8 [out_capacity]), cert (a segments.CERT_DTYPE scalar), status
+        (uint32 [1, 4]), entries (uint32 [out_entries_cap, 4]), n_entries, work
+        (uint64 [out_entries_cap]), moved (segments.REPLAY_REF_DTYPE
+        [out_entries_cap] or None), usage, summary, batch.  Every output array
+        starts as bytes of `fill`.  Raises RamcrcError (code EINVAL) for bad
+        arguments and where the survivors do not fit; in the latter case the
+        table is spoiled and the exception carries the dict as `.outputs`."""
+        from . import segments as _seg
+        victims = np.ascontiguousarray(victims, np.uint32).reshape(-1)
+        ecap = int(out_entries_cap)
+
+        def mk(shape, dt):
+            nbytes = int(np.prod(shape)) * np.dtype(dt).itemsize
+            return np.full(nbytes, fill, np.uint8).view(dt).reshape(shape)
+
+        out = mk((int(out_capacity),), np.uint8)
+        cert = mk((1,), _seg.CERT_DTYPE)
+        status = mk((1, 4), np.uint32)
+        entries = mk((ecap, 4), np.uint32)
+        n_entries = mk((1,), np.uint64)
+        work = mk((ecap,), np.uint64)
+        moved = mk((ecap,), _seg.REPLAY_REF_DTYPE) if want_moved else None
+        usage = mk((victims.size,), _seg.CLEAN_USAGE_DTYPE)
+        summary = mk((1,), _seg.CLEAN_SUMMARY_DTYPE)
+        none = 0xFFFFFFFF
+        batch = _c.c_uint32(none)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_clean_host(
+            self._h, p(victims), victims.size, p(out), out.size, _c.c_void_p(cert.ctypes.data),
+            _c.c_void_p(status.ctypes.data), p(entries), ecap, _c.c_void_p(n_entries.ctypes.data),
+            p(work), p(moved), p(usage), _c.c_void_p(summary.ctypes.data), _c.byref(batch))
+        res = dict(out=out, cert=cert[0], status=status, entries=entries, n_entries=n_entries,
+                   work=work, moved=moved, usage=usage, summary=summary[0], batch=batch.value)
+        if batch.value != none:   # the number is taken: the victims are retired
+            for b in victims:
+                self._keep[int(b)] = None
+            # the rows the table reads: those past the count hold the fill
+            n = 0 if int(summary[0]["spoiled"]) else int(n_entries[0])
+            self._keep.append((out, status, entries[:n], None, work[:n]))
+        try:
+            _check(rc, "ramcrc_replay_table_clean_host")
+        except RamcrcError as e:
+            if batch.value != none:   # (not an argument error: the call ran and refused)
+                e.outputs = res
+            raise
+        return res
 
 
 # ---------------------------------------------------------------- device
@@ -1198,6 +1282,76 @@ class ReplayTable:
             _ptr(refs), _ptr(old), _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_remove_device")
         return out
+
+    @staticmethod
+    def clean_reserve(entries_caps):
+        """The max_chunks argument of Context.reserve after which clean and
+        clean_size over victims of these record-table capacities do not
+        allocate (include/ramcrc.h, rule 11)."""
+        caps = [int(x) for x in entries_caps]
+        return 2 * (len(caps) + 16 + 16 * sum((x + 255) // 256 for x in caps))
+
+    def clean_size(self, victims, summary, usage=None, stream=None):
+        """What clean(victims) would need and move now
+        (ramcrc_replay_table_clean_size_device); changes nothing.  victims: a
+        sequence of batch numbers; summary: int64 CUDA [14] out
+        (segments.CLEAN_SUMMARY_DTYPE); usage: int64 CUDA [n_victims, 4] out
+        (segments.CLEAN_USAGE_DTYPE) or None.  Asynchronous."""
+        vic = np.ascontiguousarray(victims, np.uint32).reshape(-1)
+        nbytes = lambda x: x.numel() * x.element_size()
+        if summary is None or nbytes(summary) < 112:
+            raise RamcrcError("ReplayTable.clean_size: summary is missing or too small")
+        if usage is not None and nbytes(usage) < 32 * vic.size:
+            raise RamcrcError("ReplayTable.clean_size: usage is smaller than the victims")
+        rc = lib().ramcrc_replay_table_clean_size_device(
+            self._h, _c.c_void_p(vic.ctypes.data) if vic.size else None, vic.size, _ptr(usage),
+            _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_clean_size_device")
+        return summary
+
+    def clean(self, victims, out, out_cert, out_status, out_entries, out_n_entries, out_work,
+              summary, moved=None, usage=None, out_capacity=None, stream=None):
+        """Clean batches out of the table on the device
+        (ramcrc_replay_table_clean_device): the victims' live records move to
+        out, which becomes the next batch with out_status (int32 CUDA [1, 4]),
+        out_entries (int32 CUDA [cap, 4]), out_n_entries (int64 CUDA [1]) and
+        out_work (int64 CUDA [cap]) as a walk and an add would leave them, and
+        out_cert (int32 CUDA [2]) as certify would.  out: uint8 CUDA, 16-byte
+        aligned (out_capacity, a multiple of 16; default out.numel()); moved:
+        int32 CUDA [cap, 2] out (segments.REPLAY_REF_DTYPE) or None; usage,
+        summary as clean_size takes them.  The outputs must stay allocated and
+        unchanged like an added batch's; the table drops its references to the
+        victims' tensors, which are the caller's again once the stream has
+        passed the call.  Returns the survivor batch's number.  Asynchronous;
+        survivors that do not fit spoil the table (Context.check())."""
+        vic = np.ascontiguousarray(victims, np.uint32).reshape(-1)
+        nbytes = lambda x: x.numel() * x.element_size()
+        if out_capacity is None:
+            out_capacity = 0 if out is None else nbytes(out)
+        if out_capacity and (out is None or nbytes(out) < out_capacity):
+            raise RamcrcError("ReplayTable.clean: out is smaller than out_capacity")
+        ecap = 0 if out_entries is None else out_entries.shape[0]
+        if ecap and (out_work is None or out_work.numel() < ecap):
+            raise RamcrcError("ReplayTable.clean: out_work is smaller than the record table")
+        if moved is not None and nbytes(moved) < 8 * ecap:
+            raise RamcrcError("ReplayTable.clean: moved is smaller than the record table")
+        if usage is not None and nbytes(usage) < 32 * vic.size:
+            raise RamcrcError("ReplayTable.clean: usage is smaller than the victims")
+        for name, x, need in (("out_cert", out_cert, 8), ("out_status", out_status, 16),
+                              ("out_n_entries", out_n_entries, 8), ("summary", summary, 112)):
+            if x is not None and nbytes(x) < need:
+                raise RamcrcError(f"ReplayTable.clean: {name} is too small")
+        batch = _c.c_uint32(0)
+        rc = lib().ramcrc_replay_table_clean_device(
+            self._h, _c.c_void_p(vic.ctypes.data) if vic.size else None, vic.size,
+            _ptr(out) if out_capacity else None, int(out_capacity), _ptr(out_cert), _ptr(out_status),
+            _ptr(out_entries), ecap, _ptr(out_n_entries), _ptr(out_work), _ptr(moved), _ptr(usage),
+            _ptr(summary), _c.byref(batch), _stream(stream))
+        _check(rc, "ramcrc_replay_table_clean_device")
+        for b in vic:
+            self._keep[int(b)] = None
+        self._keep.append((out, out_status, out_entries, out_n_entries, None, out_work))
+        return batch.value
 
 
 # ------------------------------------------------------------ multi-GPU shard

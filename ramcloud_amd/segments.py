@@ -97,6 +97,13 @@ REMOVE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "removed", "ok_absent", "doesnt_exist", "object_exists", "wrong_version", "bad",
     "retry_duplicate", "retry_full", "next_version", "out_bytes", "tombstone_bytes", "spoiled")])
 REMOVE_REF_NONE = 0xFFFFFFFF
+# ramcrc_clean_usage and ramcrc_clean_summary (ramcrc_replay_table_clean_device / _host)
+CLEAN_USAGE_DTYPE = np.dtype([(n, "<u8") for n in (
+    "records", "live_objects", "live_tombstones", "live_bytes")])
+CLEAN_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "victims", "records", "moved_objects", "moved_tombstones", "object_bytes", "tombstone_bytes",
+    "dropped_objects", "dropped_tombstones", "dropped_other", "needed_bytes", "needed_records",
+    "out_bytes", "batch", "spoiled")])
 CERT_DTYPE = np.dtype([("head", "<u4"), ("checksum", "<u4")])
 STATUS_RETRY = 17
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
