@@ -480,6 +480,36 @@ class ReplayTable {
               "ramcrc_replay_table_remove_device");
     }
 
+    /// MasterService::multiIncrement (src/MasterService.cc:1277-1330) for
+    /// nReqs keys, on the device: per request the lookup above and the
+    /// RejectRules as MasterService::incrementObject applies them, the key's
+    /// 8-byte value read out of the added segments (zero for a key without an
+    /// object), d_args[q]'s integer and then its double added to it, and from
+    /// there multiWrite's steps for the object that holds the new value: the
+    /// version, the object with its checksum and the tombstone of the object
+    /// it replaces, appended to d_out.  d_parts is the reply's body, nReqs
+    /// packed MultiOp::Response::IncrementPart; *d_outCert seals d_out.  The
+    /// table is not changed: walk d_out with *d_outCert and add() it as the
+    /// next batch; several increments of one key go into several calls.
+    /// d_summary->next_version is the safeVersion to go on with.  d_keyHash,
+    /// d_rules, d_batchSegmentId, d_refs and d_old are nullable.  d_out must
+    /// not overlap an input.
+    void
+    multiIncrement(const void* d_keys, uint64_t keysBytes, const ramcrc_lookup_key* d_reqs,
+                   uint64_t nReqs, const ramcrc_increment_arg* d_args, const uint64_t* d_keyHash,
+                   const ramcrc_reject_rules* d_rules, uint64_t nextVersion, uint32_t timestamp,
+                   const uint64_t* d_batchSegmentId, void* d_out, uint32_t outCapacity,
+                   ramcrc_seg_cert* d_outCert, void* d_parts, ramcrc_write_ref* d_refs,
+                   ramcrc_lookup_result* d_old, ramcrc_increment_summary* d_summary,
+                   void* stream = NULL)
+    {
+        check(ramcrc_replay_table_increment_device(table, d_keys, keysBytes, d_reqs, nReqs, d_args,
+                                                   d_keyHash, d_rules, nextVersion, timestamp,
+                                                   d_batchSegmentId, d_out, outCapacity, d_outCert,
+                                                   d_parts, d_refs, d_old, d_summary, stream),
+              "ramcrc_replay_table_increment_device");
+    }
+
     /// What clean(victims) would move and need now: per victim batch its
     /// records and live objects, tombstones and entry bytes (d_usage,
     /// nullable), and the summary whose needed_bytes and needed_records size

@@ -1003,9 +1003,9 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
  * much, a write of up to n requests does not allocate.  The call is
  * stream-ordered and asynchronous; lifetime and concurrency are the table's.
  *
- * Not done: multiIncrement (the request's `reserved` word is where an
- * operation code would go; multiRemove is ramcrc_replay_table_remove_device,
- * below); several output segments per call and a
+ * Not done here: multiRemove is ramcrc_replay_table_remove_device and
+ * multiIncrement is ramcrc_replay_table_increment_device, both below (the
+ * request's `reserved` word stays 0); several output segments per call and a
  * SEGHEADER entry; RpcResult records; index entries; STATUS_UNKNOWN_TABLET and
  * transaction locks (the caller answers those before the call, as for the
  * read); incrementWriteCount; any change to the table itself. */
@@ -1150,7 +1150,8 @@ int ramcrc_replay_table_write_host(ramcrc_replay_table_host* t, const void* data
  * much, a remove of up to n requests does not allocate.  The call is
  * stream-ordered and asynchronous; lifetime and concurrency are the table's.
  *
- * Not done: multiIncrement; several output segments per call and a SEGHEADER
+ * Not done (multiIncrement is ramcrc_replay_table_increment_device, below):
+ * several output segments per call and a SEGHEADER
  * entry; RpcResult records; index entries (d_old says where the removed object
  * lies); STATUS_UNKNOWN_TABLET and transaction locks (the caller answers those
  * before the call, as for the read); any change to the table itself. */
@@ -1185,6 +1186,151 @@ int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* key
                                     const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
                                     ramcrc_seg_cert* out_cert, void* parts, uint32_t* refs,
                                     ramcrc_lookup_result* old, ramcrc_remove_summary* summary);
+
+/* A multi-increment: the loop of MasterService::multiIncrement
+ * (src/MasterService.cc:1277-1330) over incrementObject (:678-790), against
+ * the replay table.  The call does not change the table.  It reads each key's
+ * 8-byte value out of the added segments, adds to it, and produces one sealed
+ * log segment with the new objects and the tombstones of the objects they
+ * replace, exactly as a multi-write of the new values would; the caller walks
+ * that segment (ramcrc_segments_walk_device with *d_out_cert) and adds it as
+ * the next batch.  Reads between the increment and the add see the old state.
+ * Rules marked "ours" cover what the batch form must decide and the reference
+ * does not.
+ *
+ * Requests.  Request q is a lookup query, as the remove's: the table and
+ * key_len key bytes at d_keys + key_off, at any byte.  d_args[q] holds its two
+ * summands; d_rules[q], where given, its RejectRules as the read takes them.
+ * The host form is the definition: one loop in request order.
+ *
+ *   1. Usable: the remove's step 1.  A request is bad --
+ *      STATUS_REQUEST_FORMAT_ERROR (9), version 0 -- when the lookup would
+ *      answer RAMCRC_LOOKUP_BAD_KEY for it or d_rules[q].reserved != 0.
+ *      Nothing of the key buffer or the table is read for it.
+ *   2. Duplicates (ours, the write's and the remove's rule).  Among the usable
+ *      requests of one call the one with the lowest index is the only one
+ *      served for its key.  Every later one gets STATUS_RETRY (17), version 0,
+ *      and writes nothing, whatever became of the first.  Chaining several
+ *      increments of one key within a call is not done: the caller adds the
+ *      output and calls again.
+ *   3. Read (readObject, src/ObjectManager.cc:340-351).  w is the key's winner
+ *      as the lookup returns it now.  w not an object (absent, or a tombstone):
+ *      STATUS_OBJECT_DOESNT_EXIST (3), version 0, if doesnt_exist is set (:697,
+ *      :707); otherwise the old value is eight zero bytes, cur = 0, and the
+ *      request goes on to step 5 (:707-712): no other rule applies.  w an
+ *      object: cur = w.version, whatever its value, and the status is
+ *      rejectOperation(rules, cur) verbatim; ours: a rejected request gets that
+ *      status with version cur (the reference leaves the part's version unset).
+ *   4. Eight bytes (:716-722).  A found object whose value_len != 8 gets
+ *      STATUS_INVALID_OBJECT (22), version cur, and nothing is written; ours:
+ *      lengths below 8 too, which the reference dereferences before it tests
+ *      them.  The old value is the 8 bytes at the lookup's {batch, segment,
+ *      value_off}, at any byte alignment.
+ *   5. The sum (:741-749), on the old value's bits.  If add_int64 != 0 it is
+ *      added as a two's-complement 64-bit integer that wraps.  Then, if
+ *      add_double != 0.0, the bits are taken as an IEEE binary64 and add_double
+ *      is added: round to nearest even, subnormals kept.  The comparison means
+ *      that -0.0 adds nothing and that a NaN does add.  Ours: every NaN result
+ *      is stored as 0x7FF8000000000000, so that host and device agree bit for
+ *      bit.
+ *   6. The object (:752-756).  Its keysAndValue image is {u8 1, u16 key_len,
+ *      the key, the 8 new bytes}, 11 + key_len bytes; secondary keys of the old
+ *      object are dropped, as in the reference.  From here on the request is
+ *      steps 5-7 of ramcrc_replay_table_write_device with this image and cur
+ *      (0 unless w is an object): the version with its allocation rank and
+ *      tombstone rule, the object entry with its checksum, the old object's
+ *      tombstone behind it only when cur != 0, the space check and the cut with
+ *      STATUS_RETRY.  The updateRejectRules of :757-758 can never fire in a
+ *      batch: nothing changes the table between the read and the write.
+ *   7. The part.  d_parts: n_reqs packed 20-byte
+ *      MultiOp::Response::IncrementPart, {u32 status, u64 version, u64 new
+ *      value} little-endian (src/WireFormat.h:1124-1138).  A STATUS_OK part
+ *      holds the new value's bits; every other part holds the bits of the
+ *      request's add_double there, which :1319-1320 assign last.
+ *
+ * Outputs.  d_refs, d_old, *d_out_cert and d_out are the write's: where the
+ * entry headers lie, the lookup's answer for the key (BAD_KEY for a request
+ * that is not usable), Segment::getAppendedLength's certificate, an output that
+ * starts empty.
+ *
+ * Summary.  Requests by outcome: ok, of which created (STATUS_OK without a
+ * tombstone), the three rejections, invalid_object, bad, retry_duplicate,
+ * retry_full; tombstones; allocated; next_version (the write's rule);
+ * out_bytes; object_bytes and tombstone_bytes, payload bytes of the written
+ * entries; value_bytes (8 per OK request) and key_bytes (3 + key_len each).  On
+ * a spoiled table only the summary is written, all zero with spoiled = 1.
+ * n_reqs = 0 writes a zeroed summary with next_version passed through and the
+ * certificate of an empty segment.
+ *
+ * RAMCRC_EINVAL before any launch: t, d_out_cert or d_summary NULL; d_reqs,
+ * d_args or d_parts NULL with n_reqs > 0; d_keys NULL with keys_bytes > 0;
+ * d_out NULL with out_capacity > 0; next_version = 0; n_reqs >= 2^32 - 1;
+ * misaligned d_reqs (8), d_args (8), d_key_hash (8), d_rules (8),
+ * d_batch_segment_id (8), d_out_cert (4), d_parts (4), d_refs (8), d_old (16)
+ * or d_summary (8).  d_keys and d_out need no alignment.  d_out must not
+ * overlap any input; the call cannot check this.  Key bytes are fetched as the
+ * aligned 16-byte words that hold at least one byte of a usable request's key,
+ * the old value as the one or two aligned 16-byte words that hold it, inside
+ * its segment.  The call reads the table and the added batches' segments and
+ * writes only its outputs: no table word changes.
+ *
+ * Scratch comes from the context: with s = the grouping table's slots (the
+ * smallest power of two >= max(64, 2 n)), 64 + 12 * ceil(n / 256) words and 7 *
+ * n + s entries.  After ramcrc_ctx_reserve(ctx, 64 + 12 * ceil(n / 256),
+ * 7 * n + s), or after any earlier call on the context that reserved as much,
+ * an increment of up to n requests does not allocate.  The call is
+ * stream-ordered and asynchronous; lifetime and concurrency are the table's.
+ *
+ * Not done: chained increments of one key within a call; several output
+ * segments per call and a SEGHEADER entry; RpcResult records and
+ * linearizability; index entries; STATUS_UNKNOWN_TABLET and transaction locks;
+ * the single-object increment RPC's response header; any change to the table
+ * itself. */
+#define RAMCRC_STATUS_INVALID_OBJECT 22u        /* src/Status.h */
+
+typedef struct ramcrc_increment_arg {
+    int64_t add_int64;    /* 0: no integer addition */
+    double add_double;    /* 0.0 or -0.0: no floating-point addition */
+} ramcrc_increment_arg;   /* 16 bytes */
+
+typedef struct ramcrc_increment_summary {
+    uint64_t ok;
+    uint64_t created;          /* of ok: written without a tombstone */
+    uint64_t doesnt_exist, object_exists, wrong_version, invalid_object, bad, retry_duplicate, retry_full;
+    uint64_t tombstones;       /* written */
+    uint64_t allocated;        /* versions taken from next_version on */
+    uint64_t next_version;     /* the caller's safeVersion after the call */
+    uint64_t out_bytes;        /* the output's head */
+    uint64_t object_bytes;     /* payload bytes of the written objects */
+    uint64_t tombstone_bytes;  /* and of the written tombstones */
+    uint64_t value_bytes;      /* 8 per OK request */
+    uint64_t key_bytes;        /* keysAndValueLength - valueLength, same requests */
+    uint64_t spoiled;
+} ramcrc_increment_summary;
+
+int ramcrc_replay_table_increment_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                         const ramcrc_lookup_key* d_reqs, uint64_t n_reqs,
+                                         const ramcrc_increment_arg* d_args,
+                                         const uint64_t* d_key_hash /* nullable */,
+                                         const ramcrc_reject_rules* d_rules /* nullable: no rules */,
+                                         uint64_t next_version, uint32_t timestamp,
+                                         const uint64_t* d_batch_segment_id /* nullable */,
+                                         void* d_out, uint32_t out_capacity, ramcrc_seg_cert* d_out_cert,
+                                         void* d_parts, ramcrc_write_ref* d_refs /* nullable */,
+                                         ramcrc_lookup_result* d_old /* nullable */,
+                                         ramcrc_increment_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_increment_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                       const ramcrc_lookup_key* reqs, uint64_t n_reqs,
+                                       const ramcrc_increment_arg* args,
+                                       const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                       uint64_t next_version, uint32_t timestamp,
+                                       const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                       ramcrc_seg_cert* out_cert, void* parts, ramcrc_write_ref* refs,
+                                       ramcrc_lookup_result* old, ramcrc_increment_summary* summary);
 
 /* Cleaning batches out of the table: the log cleaner's relocation step
  * (LogCleaner::relocateLiveEntries, src/LogCleaner.cc:575-722, over

@@ -358,6 +358,38 @@ __global__ __launch_bounds__(kPartThreads) void k_rm_scan(RtabDesc a, RmDesc w)
 }
 
 // --------------------------------------------------------------- k_rm_emit
+// One lane's entry from registers: the first `size` bytes (at least 4, at most
+// 4 kWords - 3) of the little-endian words x[0 .. kWords / 2] to e (any
+// residue), as aligned 32-bit words with byte stores only in front of the first
+// and behind the last.  Every store lies inside [e, e + size).
+template <uint32_t kWords>
+__device__ __forceinline__ void lane_store_entry(uint64_t e, const uint64_t* x, uint32_t size)
+{
+    typedef __attribute__((address_space(1))) uint8_t gw8;
+    typedef __attribute__((address_space(1))) uint32_t gw32;
+    const uint32_t lead = (4u - uint32_t(e)) & 3u;
+#pragma unroll
+    for (uint32_t b = 0; b < 3; b++)
+        if (b < lead)
+            *reinterpret_cast<gw8*>(e + b) = uint8_t(x[0] >> (8 * b));
+    const uint32_t nd = (size - lead) >> 2, rem = (size - lead) & 3u;
+    const uint64_t at = e + lead;
+#pragma unroll
+    for (uint32_t k = 0; k < kWords; k++) {
+        const uint32_t lo = uint32_t(x[k >> 1] >> (32 * (k & 1)));
+        const uint32_t hi = uint32_t(x[(k + 1) >> 1] >> (32 * ((k + 1) & 1)));
+        const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, lead);
+        if (k < nd) {
+            *reinterpret_cast<gw32*>(at + 4 * k) = v;
+        } else if (k == nd) {
+#pragma unroll
+            for (uint32_t b = 0; b < 3; b++)
+                if (b < rem)
+                    *reinterpret_cast<gw8*>(at + 4 * k + b) = uint8_t(v >> (8 * b));
+        }
+    }
+}
+
 // One tombstone of a key of at most kRmLaneKeyMax bytes, by one lane: the
 // whole entry at e (any residue) -- two metadata bytes, the header, the
 // checksum, the key.  The key is read once, as aligned 16-byte words; the
@@ -369,8 +401,6 @@ __device__ __forceinline__ void rm_tombstone_lane(uint64_t e, uint64_t key, uint
                                                   uint32_t ts, const uint32_t* t0)
 {
     namespace rw = ramcrc_write;
-    typedef __attribute__((address_space(1))) uint8_t gw8;
-    typedef __attribute__((address_space(1))) uint32_t gw32;
     constexpr uint32_t kKw = (kRmLaneKeyMax + 7) / 8;
     constexpr uint32_t kWords = (2 + rw::kTombHeader + kRmLaneKeyMax + 3) / 4;   // 18
     static_assert(kRmLaneKeyMax % 8 != 0 && kRmLaneKeyMax % 8 <= 6, "the last key word's top two bytes are 0");
@@ -402,28 +432,7 @@ __device__ __forceinline__ void rm_tombstone_lane(uint64_t e, uint64_t key, uint
         x[4 + j] = (kw[j - 1] >> 48) | (kw[j] << 16);
     x[4 + kKw] = 0;
     static_assert(4 + kKw == kWords / 2, "the words of the longest entry, and one of zeros");
-    const uint32_t size = 2 + rw::kTombHeader + klen;
-    const uint32_t lead = (4u - uint32_t(e)) & 3u;   // (size >= 34: the entry reaches an aligned word)
-#pragma unroll
-    for (uint32_t b = 0; b < 3; b++)
-        if (b < lead)
-            *reinterpret_cast<gw8*>(e + b) = uint8_t(x[0] >> (8 * b));
-    const uint32_t nd = (size - lead) >> 2, rem = (size - lead) & 3u;
-    const uint64_t at = e + lead;
-#pragma unroll
-    for (uint32_t k = 0; k < kWords; k++) {
-        const uint32_t lo = uint32_t(x[k >> 1] >> (32 * (k & 1)));
-        const uint32_t hi = uint32_t(x[(k + 1) >> 1] >> (32 * ((k + 1) & 1)));
-        const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, lead);
-        if (k < nd) {
-            *reinterpret_cast<gw32*>(at + 4 * k) = v;
-        } else if (k == nd) {
-#pragma unroll
-            for (uint32_t b = 0; b < 3; b++)
-                if (b < rem)
-                    *reinterpret_cast<gw8*>(at + 4 * k + b) = uint8_t(v >> (8 * b));
-        }
-    }
+    lane_store_entry<kWords>(e, x, 2 + rw::kTombHeader + klen);   // (34 bytes or more)
 }
 
 __global__ __launch_bounds__(kPartThreads) void k_rm_emit(RtabDesc a, RmDesc w)

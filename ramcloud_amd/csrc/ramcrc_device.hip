@@ -87,6 +87,7 @@
 #include "sidelog_rules.h"
 #include "write_rules.h"
 #include "remove_rules.h"
+#include "increment_rules.h"
 #include "clean_rules.h"
 #include "ramcrc.h"
 
@@ -113,6 +114,7 @@ using ramcrc::OpTable;
 #include "dev_replay_table.inc"
 #include "dev_write.inc"
 #include "dev_remove.inc"
+#include "dev_increment.inc"
 #include "dev_clean.inc"
 
 extern "C" {
@@ -1737,6 +1739,111 @@ int ramcrc_replay_table_remove_device(ramcrc_replay_table* t, const void* d_keys
     HIPCHK(hipGetLastError());
     // (at least one workgroup: an empty call still gets its certificate)
     hipLaunchKernelGGL(k_rm_emit, grid, dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_increment_device(ramcrc_replay_table* t, const void* d_keys, uint64_t keys_bytes,
+                                         const ramcrc_lookup_key* d_reqs, uint64_t n_reqs,
+                                         const ramcrc_increment_arg* d_args,
+                                         const uint64_t* d_key_hash, const ramcrc_reject_rules* d_rules,
+                                         uint64_t next_version, uint32_t timestamp,
+                                         const uint64_t* d_batch_segment_id, void* d_out,
+                                         uint32_t out_capacity, ramcrc_seg_cert* d_out_cert, void* d_parts,
+                                         ramcrc_write_ref* d_refs, ramcrc_lookup_result* d_old,
+                                         ramcrc_increment_summary* d_summary, void* stream)
+{
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !d_summary || !d_out_cert ||
+        (n_reqs && (!d_reqs || !d_args || !d_parts)) || (keys_bytes && !d_keys) || (out_capacity && !d_out))
+        return RAMCRC_EINVAL;
+    const uint64_t K = reinterpret_cast<uint64_t>(d_keys), O = reinterpret_cast<uint64_t>(d_out);
+    if ((reinterpret_cast<uint64_t>(d_reqs) & 7) || (reinterpret_cast<uint64_t>(d_args) & 7) ||
+        (reinterpret_cast<uint64_t>(d_key_hash) & 7) ||
+        (reinterpret_cast<uint64_t>(d_rules) & 7) || (reinterpret_cast<uint64_t>(d_batch_segment_id) & 7) ||
+        (reinterpret_cast<uint64_t>(d_out_cert) & 3) || (reinterpret_cast<uint64_t>(d_parts) & 3) ||
+        (reinterpret_cast<uint64_t>(d_refs) & 7) || (reinterpret_cast<uint64_t>(d_old) & 15) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || K > UINT64_MAX - keys_bytes ||
+        O > UINT64_MAX - out_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: the head line, k_wr_scan's summary, then the tile sums, in the
+    // chunk-partial buffer; the per-request words, then the grouping table, in
+    // the plan buffer (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_reqs + kPartThreads - 1) / kPartThreads;
+    const uint64_t gslots = ramcrc_res::slots_for(n_reqs);
+    const uint64_t head_words = 2 * kWrHeadWords + kIncSumWords;
+    int rc = reserve_locked(c, head_words + 2 * kWrTileWords * ntiles, kIncReqWords * n_reqs + gslots);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    // the group pass is the remove's, over the remove's request layout
+    RmDesc r{};
+    r.keys = K;
+    r.keys_bytes = keys_bytes;
+    r.reqs = reinterpret_cast<const uint64_t*>(d_reqs);
+    r.nq = n_reqs;
+    r.key_hash = d_key_hash;
+    r.rules = reinterpret_cast<const uint64_t*>(d_rules);
+    r.hash = c->plan_local;
+    r.slot = r.hash + n_reqs;
+    r.group = reinterpret_cast<unsigned long long*>(r.slot + 6 * n_reqs);
+    r.gslots = gslots;
+    // the records, the scan and the entries are the write's; the key buffer is its data
+    WrDesc w{};
+    w.data = K;
+    w.data_bytes = keys_bytes;
+    w.reqs = r.reqs;
+    w.nq = n_reqs;
+    w.key_hash = d_key_hash;
+    w.rules = r.rules;
+    w.batch_seg = d_batch_segment_id;
+    w.next_version = next_version;
+    w.timestamp = timestamp;
+    w.cap = out_capacity;
+    w.out = O;
+    w.cert = d_out_cert;
+    w.parts = static_cast<uint32_t*>(d_parts);   // five words each
+    w.refs = reinterpret_cast<uint2*>(d_refs);
+    w.summary = reinterpret_cast<ramcrc_write_summary*>(c->partials + 2 * kWrHeadWords);
+    w.slot = r.slot;
+    w.rec = r.slot + n_reqs;
+    w.group = r.group;   // one word a slot
+    w.gslots = gslots;
+    w.head = reinterpret_cast<unsigned long long*>(c->partials);
+    w.tile = reinterpret_cast<uint64_t*>(c->partials + head_words);
+    IncDesc x{};
+    x.args = reinterpret_cast<const uint64_t*>(d_args);
+    x.bits = w.rec + 4 * n_reqs;
+    x.summary = d_summary;
+    // the probe runs over the caller's own requests, with the group pass's
+    // hashes as the given ones
+    LookDesc q{};
+    q.keys = K;
+    q.keys_bytes = keys_bytes;
+    q.queries = w.reqs;
+    q.nq = n_reqs;
+    q.key_hash = r.hash;
+    q.results = reinterpret_cast<u32x4*>(d_old);
+    const dim3 grid(rtab_grid(c, n_reqs, kPartThreads));
+    HIPCHK(hipMemsetAsync(w.head, 0, (head_words + 2 * kWrTileWords * ntiles) * sizeof(uint32_t), s));
+    if (n_reqs) {
+        HIPCHK(hipMemsetAsync(w.group, 0, gslots * sizeof(uint64_t), s));
+        if (d_key_hash)
+            hipLaunchKernelGGL(k_rm_group<true>, grid, dim3(kPartThreads), 0, s, a, r);
+        else
+            hipLaunchKernelGGL(k_rm_group<false>, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_inc_size, grid, dim3(kPartThreads), 0, s, a, q, w, x);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_wr_scan, dim3(1), dim3(kPartThreads), 0, s, a, w);
+    HIPCHK(hipGetLastError());
+    // (at least one workgroup: an empty call still gets its certificate and summary)
+    hipLaunchKernelGGL(k_inc_emit, grid, dim3(kPartThreads), 0, s, a, w, x);
     HIPCHK(hipGetLastError());
     return RAMCRC_OK;
 }

@@ -32,6 +32,7 @@
 #include "sidelog_rules.h"
 #include "write_rules.h"
 #include "remove_rules.h"
+#include "increment_rules.h"
 #include "clean_rules.h"
 
 namespace {
@@ -1331,6 +1332,167 @@ int ramcrc_replay_table_remove_host(ramcrc_replay_table_host* t, const void* key
         return RAMCRC_ENOMEM;
     }
     sm.next_version = rm::next_version(next_version, top);
+    const uint32_t head = uint32_t(sm.out_bytes);
+    uint8_t lenle[4];
+    for (int b = 0; b < 4; b++)
+        lenle[b] = uint8_t(head >> (8 * b));
+    *out_cert = ramcrc_seg_cert{head, ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
+    *summary = sm;
+    return RAMCRC_OK;
+}
+
+// A multi-increment (the rules of increment_rules.h): per request the
+// duplicate test, the lookup, rejectOperation, the length test and the sum;
+// then the write's version, object and tombstone (write_rules.h) for the image
+// of the new value, appended to the one output.
+int ramcrc_replay_table_increment_host(ramcrc_replay_table_host* t, const void* keys, uint64_t keys_bytes,
+                                       const ramcrc_lookup_key* reqs, uint64_t n_reqs,
+                                       const ramcrc_increment_arg* args,
+                                       const uint64_t* key_hash, const ramcrc_reject_rules* rules,
+                                       uint64_t next_version, uint32_t timestamp,
+                                       const uint64_t* batch_segment_id, void* out, uint32_t out_capacity,
+                                       ramcrc_seg_cert* out_cert, void* parts, ramcrc_write_ref* refs,
+                                       ramcrc_lookup_result* old, ramcrc_increment_summary* summary)
+{
+    namespace rr = ramcrc_read;
+    namespace rw = ramcrc_write;
+    namespace ri = ramcrc_increment;
+    if (!t || next_version == 0 || n_reqs >= 0xFFFFFFFFull || !summary || !out_cert ||
+        (n_reqs && (!reqs || !args || !parts)) || (keys_bytes && !keys) || (out_capacity && !out))
+        return RAMCRC_EINVAL;
+    ramcrc_increment_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        *summary = sm;
+        return RAMCRC_OK;
+    }
+    const uint8_t* const kb = static_cast<const uint8_t*>(keys);
+    uint8_t* const ob = static_cast<uint8_t*>(out);
+    std::unordered_set<std::string> seen;   // table id, then the key
+    uint32_t meta = 0xFFFFFFFFu;            // the output's running metadata checksum
+    uint64_t top = 0;                       // one past the highest version the tombstone rule gave
+    bool open = true;                       // no request has failed to fit yet
+    try {
+        for (uint64_t i = 0; i < n_reqs; i++) {
+            ramcrc_lookup_key q;   // (no alignment rule)
+            memcpy(&q, reinterpret_cast<const uint8_t*>(reqs) + i * sizeof(q), sizeof(q));
+            const uint8_t* const ap = reinterpret_cast<const uint8_t*>(args) + i * sizeof(*args);
+            const uint64_t add_int = ld64(ap), add_dbl = ld64(ap + 8);
+            rr::Rules ru = rr::no_rules();
+            if (rules) {
+                const uint8_t* const p = reinterpret_cast<const uint8_t*>(rules) + i * sizeof(*rules);
+                ru = rr::Rules{ld64(p), ld64(p + 8)};
+            }
+            uint32_t status = rr::kStatusFormatError;
+            uint64_t version = 0, bits = 0;
+            ramcrc_write_ref ref{rw::kNone, rw::kNone};
+            ramcrc_lookup_result res = ramcrc_look::no_result(RAMCRC_LOOKUP_BAD_KEY);
+            if (!ri::bad_request(q.key_off, q.key_len, q.reserved, rr::bad_rules(ru), keys_bytes)) {
+                const uint8_t* const key = kb + q.key_off;
+                const uint8_t* pay = nullptr;
+                uint32_t pay_len = 0;
+                ramcrc_look::Value val{0u, 0u};
+                res = look_one(t, kb, keys_bytes, q, key_hash ? key_hash + i : nullptr, &pay, &pay_len, &val);
+                std::string id(reinterpret_cast<const char*>(&q.table_id), 8);
+                if (q.key_len)
+                    id.append(reinterpret_cast<const char*>(key), q.key_len);
+                if (!seen.insert(id).second) {
+                    status = ri::kStatusRetry;   // a later request of a key of this call
+                    sm.retry_duplicate++;
+                } else {
+                    const bool obj = res.kind == RAMCRC_LOOKUP_OBJECT;
+                    const ri::Outcome o = ri::outcome(res.kind, res.version, obj ? res.value_len : 0u, ru);
+                    const uint64_t cur = o.cur;
+                    status = o.status;
+                    version = cur;
+                    if (o.reach) {
+                        bits = ri::sum(obj ? ld64(pay + val.off) : 0ull, add_int, add_dbl);
+                        const uint32_t dl = ri::image_len(q.key_len);
+                        const uint64_t a = next_version + sm.allocated;
+                        const uint64_t v =
+                            rw::new_version(cur, res.kind == RAMCRC_LOOKUP_TOMBSTONE, res.version, a);
+                        if (cur == 0) {
+                            sm.allocated++;
+                            if (v != a && v + 1 > top)
+                                top = v + 1;
+                        }
+                        const bool with_tomb = cur != 0;
+                        const uint64_t size = rw::request_size(dl, with_tomb, q.key_len);
+                        if (open && size <= out_capacity - sm.out_bytes) {
+                            uint8_t* e = ob + sm.out_bytes;
+                            const uint32_t olen = rw::kObjHeader + dl;
+                            uint32_t nm;
+                            uint64_t m = rw::entry_meta(RAMCRC_LOG_ENTRY_TYPE_OBJ, olen, &nm);
+                            ref.object_off = uint32_t(sm.out_bytes);
+                            for (uint32_t b = 0; b < nm; b++)
+                                e[b] = uint8_t(m >> (8 * b));
+                            meta = ramcrc_update(meta, e, nm);
+                            e += nm;
+                            const auto key_byte = [key](uint32_t k) { return uint32_t(key[k]); };
+                            for (uint32_t b = 4; b < olen; b++)
+                                e[b] = uint8_t(ri::object_byte(b - 4, q.key_len, timestamp, v, q.table_id, bits,
+                                                               key_byte));
+                            const uint32_t ck = ~ramcrc_update(0xFFFFFFFFu, e + 4, olen - 4);
+                            for (int b = 0; b < 4; b++)
+                                e[b] = uint8_t(ck >> (8 * b));
+                            e += olen;
+                            if (with_tomb) {
+                                const uint32_t tlen = rw::kTombHeader + q.key_len;
+                                const uint64_t seg_id =
+                                    batch_segment_id ? batch_segment_id[res.ref.batch] + res.segment : 0ull;
+                                m = rw::entry_meta(RAMCRC_LOG_ENTRY_TYPE_OBJTOMB, tlen, &nm);
+                                ref.tombstone_off = uint32_t(e - ob);
+                                for (uint32_t b = 0; b < nm; b++)
+                                    e[b] = uint8_t(m >> (8 * b));
+                                meta = ramcrc_update(meta, e, nm);
+                                e += nm;
+                                for (uint32_t b = 0; b < 28; b++)
+                                    e[b] = uint8_t(rw::tomb_header_byte(b, q.table_id, seg_id, cur, timestamp));
+                                if (q.key_len)
+                                    memcpy(e + rw::kTombHeader, key, q.key_len);
+                                uint32_t tk = ramcrc_update(0xFFFFFFFFu, e, 28);
+                                tk = ~ramcrc_update(tk, e + rw::kTombHeader, q.key_len);
+                                for (int b = 0; b < 4; b++)
+                                    e[28 + b] = uint8_t(tk >> (8 * b));
+                                sm.tombstones++;
+                                sm.tombstone_bytes += tlen;
+                            } else {
+                                sm.created++;
+                            }
+                            sm.ok++;
+                            sm.out_bytes += size;
+                            sm.object_bytes += olen;
+                            sm.value_bytes += ri::kValueBytes;
+                            sm.key_bytes += dl - ri::kValueBytes;
+                            version = v;
+                        } else {
+                            open = false;
+                            status = ri::kStatusRetry;   // "Must wait for cleaner"
+                            sm.retry_full++;
+                        }
+                    } else {
+                        (status == rr::kStatusDoesntExist ? sm.doesnt_exist
+                         : status == rr::kStatusExists ? sm.object_exists
+                         : status == rr::kStatusWrongVersion ? sm.wrong_version : sm.invalid_object)++;
+                    }
+                }
+            } else {
+                sm.bad++;
+            }
+            const uint64_t third = ri::part_value(status, bits, add_dbl);
+            uint8_t* const p = static_cast<uint8_t*>(parts) + i * ri::kPartBytes;
+            memcpy(p, &status, 4);
+            memcpy(p + 4, &version, 8);
+            memcpy(p + 12, &third, 8);
+            if (refs)
+                memcpy(reinterpret_cast<uint8_t*>(refs) + i * sizeof(ref), &ref, sizeof(ref));
+            if (old)
+                memcpy(reinterpret_cast<uint8_t*>(old) + i * sizeof(res), &res, sizeof(res));
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.next_version = next_version + sm.allocated > top ? next_version + sm.allocated : top;
     const uint32_t head = uint32_t(sm.out_bytes);
     uint8_t lenle[4];
     for (int b = 0; b < 4; b++)

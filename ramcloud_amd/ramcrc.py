@@ -133,6 +133,10 @@ def lib():
                                                     vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_remove_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                   vp, vp, vp, vp, vp]),
+        "ramcrc_replay_table_increment_device": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp,
+                                                       u32, vp, vp, vp, vp, vp, vp]),
+        "ramcrc_replay_table_increment_host": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, u64, u32, vp, vp,
+                                                     u32, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_clean_size_device": (i32, [vp, vp, u32, vp, vp, vp]),
         "ramcrc_replay_table_clean_device": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u64, vp, vp, vp,
                                                    vp, vp, _c.POINTER(u32), vp]),
@@ -656,6 +660,54 @@ class ReplayTableHost:
             _c.c_void_p(cert.ctypes.data), p(parts), p(refs), p(old),
             _c.c_void_p(summary.ctypes.data))
         _check(rc, "ramcrc_replay_table_remove_host")
+        return out, cert[0], parts, refs, old, summary[0]
+
+    def increment(self, keys, reqs, args, out_capacity, next_version, timestamp=0, rules=None,
+                  key_hash=None, batch_segment_id=None, want_refs=True, want_old=False):
+        """A multi-increment (ramcrc_replay_table_increment_host): the table is
+        not changed; the call returns the log segment of new objects and
+        tombstones to walk and add as the next batch.  keys: uint8 [keys_bytes];
+        reqs: segments.LOOKUP_KEY_DTYPE [n] (segments.lookup_queries packs both);
+        args: segments.INCREMENT_ARG_DTYPE [n] (segments.increment_args); rules
+        and key_hash as read takes them; batch_segment_id: uint64 [batches] or
+        None.  Returns (out: uint8 [out_capacity], its bytes from the head on
+        untouched zeros; cert: a segments.CERT_DTYPE scalar; parts:
+        segments.INCREMENT_PART_DTYPE [n]; refs: segments.WRITE_REF_DTYPE [n] or
+        None; old: segments.LOOKUP_RESULT_DTYPE [n] or None; summary: a
+        segments.INCREMENT_SUMMARY_DTYPE scalar).  On a spoiled table everything
+        but the summary is the wrapper's zeros and summary["spoiled"] is 1."""
+        from . import segments as _seg
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        reqs = np.ascontiguousarray(reqs, _seg.LOOKUP_KEY_DTYPE).reshape(-1)
+        args = np.ascontiguousarray(args, _seg.INCREMENT_ARG_DTYPE).reshape(-1)
+        n = reqs.shape[0]
+        if args.size < n:
+            raise RamcrcError("ReplayTableHost.increment: fewer args than requests")
+        if key_hash is not None:
+            key_hash = np.ascontiguousarray(key_hash, np.uint64).reshape(-1)
+            if key_hash.size < n:
+                raise RamcrcError("ReplayTableHost.increment: fewer hashes than requests")
+        if rules is not None:
+            rules = np.ascontiguousarray(rules, _seg.REJECT_RULES_DTYPE).reshape(-1)
+            if rules.size < n:
+                raise RamcrcError("ReplayTableHost.increment: fewer rules than requests")
+        if batch_segment_id is not None:
+            batch_segment_id = np.ascontiguousarray(batch_segment_id, np.uint64).reshape(-1)
+            if batch_segment_id.size < len(self._keep):
+                raise RamcrcError("ReplayTableHost.increment: fewer segment ids than batches")
+        out = np.zeros(int(out_capacity), np.uint8)
+        cert = np.zeros(1, _seg.CERT_DTYPE)
+        parts = np.zeros(n, _seg.INCREMENT_PART_DTYPE)
+        refs = np.zeros(n, _seg.WRITE_REF_DTYPE) if want_refs else None
+        old = np.zeros(n, _seg.LOOKUP_RESULT_DTYPE) if want_old else None
+        summary = np.zeros(1, _seg.INCREMENT_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_increment_host(
+            self._h, p(keys), keys.size, p(reqs), n, p(args), p(key_hash), p(rules), int(next_version),
+            int(timestamp), p(batch_segment_id), p(out), out.size,
+            _c.c_void_p(cert.ctypes.data), p(parts), p(refs), p(old),
+            _c.c_void_p(summary.ctypes.data))
+        _check(rc, "ramcrc_replay_table_increment_host")
         return out, cert[0], parts, refs, old, summary[0]
 
     def clean_size(self, victims):
@@ -1281,6 +1333,52 @@ class ReplayTable:
             _ptr(out) if out_capacity else None, int(out_capacity), _ptr(out_cert), _ptr(parts),
             _ptr(refs), _ptr(old), _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_remove_device")
+        return out
+
+    def increment(self, keys, reqs, args, out, out_cert, parts, summary, next_version, timestamp=0,
+                  rules=None, key_hash=None, batch_segment_id=None, refs=None, old=None,
+                  keys_bytes=None, n_reqs=None, out_capacity=None, stream=None):
+        """A multi-increment on the device
+        (ramcrc_replay_table_increment_device): the table is not changed; out
+        becomes the log segment of new objects and tombstones to walk (with
+        out_cert) and add as the next batch.  keys, reqs as remove takes them;
+        args: CUDA holding n segments.INCREMENT_ARG_DTYPE records (16 bytes
+        each, 8-byte aligned); out: uint8 CUDA out, any alignment (out_capacity
+        default out.numel()); out_cert: int32 CUDA [2] out (segments.CERT_DTYPE);
+        parts: CUDA out, 20 bytes a request (segments.INCREMENT_PART_DTYPE),
+        4-byte aligned; summary: int64 CUDA [18] out
+        (segments.INCREMENT_SUMMARY_DTYPE); rules, key_hash as read takes them;
+        batch_segment_id: int64 CUDA [batches] or None; refs: int32 CUDA [n, 2]
+        out or None; old: CUDA out as lookup's results or None.  Asynchronous."""
+        nbytes = lambda x: x.numel() * x.element_size()
+        if keys_bytes is None:
+            keys_bytes = 0 if keys is None else nbytes(keys)
+        if n_reqs is None:
+            n_reqs = 0 if reqs is None else nbytes(reqs) // 24
+        if out_capacity is None:
+            out_capacity = 0 if out is None else nbytes(out)
+        if out_capacity and (out is None or nbytes(out) < out_capacity):
+            raise RamcrcError("ReplayTable.increment: out is smaller than out_capacity")
+        if n_reqs and (args is None or nbytes(args) < 16 * n_reqs):
+            raise RamcrcError("ReplayTable.increment: fewer args than requests")
+        if n_reqs and (parts is None or nbytes(parts) < 20 * n_reqs):
+            raise RamcrcError("ReplayTable.increment: parts is smaller than the requests")
+        if refs is not None and nbytes(refs) < 8 * n_reqs:
+            raise RamcrcError("ReplayTable.increment: refs is smaller than the requests")
+        if old is not None and nbytes(old) < 32 * n_reqs:
+            raise RamcrcError("ReplayTable.increment: old is smaller than the requests")
+        if rules is not None and nbytes(rules) < 16 * n_reqs:
+            raise RamcrcError("ReplayTable.increment: fewer rules than requests")
+        if key_hash is not None and key_hash.numel() < n_reqs:
+            raise RamcrcError("ReplayTable.increment: fewer hashes than requests")
+        if out_cert is None or nbytes(out_cert) < 8 or summary is None or nbytes(summary) < 144:
+            raise RamcrcError("ReplayTable.increment: out_cert or summary is missing or too small")
+        rc = lib().ramcrc_replay_table_increment_device(
+            self._h, _ptr(keys) if keys_bytes else None, int(keys_bytes), _ptr(reqs), int(n_reqs),
+            _ptr(args), _ptr(key_hash), _ptr(rules), int(next_version), int(timestamp),
+            _ptr(batch_segment_id), _ptr(out) if out_capacity else None, int(out_capacity),
+            _ptr(out_cert), _ptr(parts), _ptr(refs), _ptr(old), _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_increment_device")
         return out
 
     @staticmethod

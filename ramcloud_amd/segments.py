@@ -97,6 +97,17 @@ REMOVE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "removed", "ok_absent", "doesnt_exist", "object_exists", "wrong_version", "bad",
     "retry_duplicate", "retry_full", "next_version", "out_bytes", "tombstone_bytes", "spoiled")])
 REMOVE_REF_NONE = 0xFFFFFFFF
+# ramcrc_increment_arg, the packed MultiOp::Response::IncrementPart and
+# ramcrc_increment_summary (ramcrc_replay_table_increment_device / _host); a
+# request is a LOOKUP_KEY_DTYPE record, its reference a WRITE_REF_DTYPE record.
+# The double and the new value are kept as bits: a NaN's payload is data here.
+INCREMENT_ARG_DTYPE = np.dtype([("add_int64", "<i8"), ("add_double_bits", "<u8")])
+INCREMENT_PART_DTYPE = np.dtype([("status", "<u4"), ("version", "<u8"), ("value_bits", "<u8")])   # packed
+INCREMENT_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "ok", "created", "doesnt_exist", "object_exists", "wrong_version", "invalid_object", "bad",
+    "retry_duplicate", "retry_full", "tombstones", "allocated", "next_version", "out_bytes",
+    "object_bytes", "tombstone_bytes", "value_bytes", "key_bytes", "spoiled")])
+STATUS_INVALID_OBJECT = 22
 # ramcrc_clean_usage and ramcrc_clean_summary (ramcrc_replay_table_clean_device / _host)
 CLEAN_USAGE_DTYPE = np.dtype([(n, "<u8") for n in (
     "records", "live_objects", "live_tombstones", "live_bytes")])
@@ -178,6 +189,37 @@ def write_requests(objects, align=1):
         parts.append(b"\0" * pad + image)
         at += pad + len(image)
     return np.frombuffer(b"".join(parts), np.uint8).copy(), q
+
+
+def double_bits(x):
+    """The bits of a binary64: of a float, or an int that already is the bits."""
+    if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+        return int(x) & 0xFFFFFFFFFFFFFFFF
+    return int(np.array(x, "<f8").view("<u8"))
+
+
+def increment_args(args):
+    """INCREMENT_ARG_DTYPE [n] from one (add_int64, add_double) pair per
+    request.  add_int64: any int, taken modulo 2^64; add_double: a float, or an
+    int holding the bits of one (for a NaN with a payload, or -0.0)."""
+    a = np.zeros(len(args), INCREMENT_ARG_DTYPE)
+    for i, (add_int, add_double) in enumerate(args):
+        v = int(add_int) & 0xFFFFFFFFFFFFFFFF
+        a["add_int64"][i] = v - (1 << 64) if v >> 63 else v
+        a["add_double_bits"][i] = double_bits(add_double)
+    return a
+
+
+def multi_increment_parts(parts, n=None):
+    """A multi-increment's parts (bytes or a uint8 array of packed 20-byte
+    records) as INCREMENT_PART_DTYPE [n]; its value_bits viewed as int64 or
+    float64 is the part's newValue."""
+    raw = np.ascontiguousarray(parts).view(np.uint8).reshape(-1).tobytes() \
+        if not isinstance(parts, (bytes, bytearray)) else bytes(parts)
+    n = len(raw) // 20 if n is None else int(n)
+    if 20 * n > len(raw):
+        raise ValueError("multi_increment_parts: fewer than n parts")
+    return np.frombuffer(raw, INCREMENT_PART_DTYPE, n).copy()
 
 
 def read_rules(rules):
