@@ -429,6 +429,28 @@ class ReplayTable {
               "ramcrc_replay_table_read_device");
     }
 
+    /// The reply of MasterService::readHashes (src/MasterService.cc:797-809)
+    /// over ObjectManager::readHashes (src/ObjectManager.cc:179-265), packed
+    /// on the device: for each of the nHashes primary-key hashes an
+    /// IndexLookup got from its indexlet, every object of tableId whose
+    /// primary-key hash equals it, as {u64 version, u32 length} and the
+    /// object's keys and value, back to back from d_reply.  A hash is answered
+    /// while the reply so far is at most maxLength (maxResponseRpcLen less
+    /// sizeof(WireFormat::ReadHashes::Response)) and its parts end within
+    /// replyCapacity.  d_summary->hashes is respHdr->numHashes and
+    /// d_summary->objects the objects in the reply.  d_parts is nullable.
+    /// Read-only on the table; d_reply must not overlap an added batch.
+    void
+    readHashes(uint64_t tableId, const uint64_t* d_hashes, uint64_t nHashes, void* d_reply,
+               uint64_t replyCapacity, uint64_t maxLength, ramcrc_hash_part* d_parts,
+               ramcrc_read_hashes_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_read_hashes_device(table, tableId, d_hashes, nHashes, 0u, d_reply,
+                                                     replyCapacity, maxLength, d_parts, d_summary,
+                                                     stream),
+              "ramcrc_replay_table_read_hashes_device");
+    }
+
     /// MasterService::multiWrite (src/MasterService.cc:1523-1601) for nReqs
     /// keysAndValue images, on the device: per request the lookup above, the
     /// RejectRules, the new version as ObjectManager::writeObject chooses it

@@ -904,6 +904,122 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
                                   uint64_t* part_off, ramcrc_lookup_result* results,
                                   ramcrc_read_summary* summary);
 
+/* An indexed read's reply: the loop of MasterService::readHashes
+ * (src/MasterService.cc:797-809) over ObjectManager::readHashes
+ * (src/ObjectManager.cc:179-265), against the replay table.  IndexLookup gets
+ * primary-key hashes from an indexlet and sends READ_HASHES to the master; the
+ * call answers it: for every asked 64-bit hash, every object whose primary-key
+ * hash equals it, packed back to back into d_reply.  No key is given and none
+ * is compared.  Rules marked "ours" cover what the reference leaves open or
+ * where this form differs from it.
+ *
+ * A record's hash is d_key_hash[record] of its batch when that batch was added
+ * with hashes, and Key::getHash of its key, computed in the call, otherwise
+ * (the survivor batch of a clean has none).  The asked hashes must be the
+ * same function of (table id, key) that the adds used.  A table whose adds
+ * were given anything but Key::getHash must not have been cleaned when this
+ * call is made: otherwise which of the moved keys are found is unspecified.
+ * Nothing wrong is ever returned: every object sent has a record hash equal to
+ * the asked hash.  In the reference the asked value is Object::getPKHash(),
+ * Key::getHash of key 0; the table's key already is an object's first key.
+ *
+ * Match.  For asked hash h the call walks the slots from h & (slots - 1) to
+ * the first unclaimed one, at most every slot once: slots are never
+ * un-claimed, so every key of h lies there.  A claimed slot matches when its
+ * claimant's table id equals table_id -- ours: all 64 bits; the reference
+ * compares only the hash (:241), and Key::getHash is seeded with the low 32
+ * bits of the id -- and its claimant's record hash equals h.  A matching
+ * slot's winner is the key's, exactly as the lookup names it: a tombstone
+ * sends nothing (:235) and counts in `tombstones`, an object sends one part.
+ *
+ * Part.  12 bytes little-endian, {u64 version, u32 length} (:243-245), then
+ * `length` bytes: the winner's payload [24, payload length), as
+ * appendKeysAndValueToBuffer writes it; an object whose keys run past its
+ * payload still sends its payload from byte 24, as the read does.  Parts lie
+ * back to back from d_reply + 0 in the order of the asked hashes, so a part
+ * may begin at any byte.  Ours: the objects of one hash go in ascending winner
+ * {batch, record}, batch first (the reference's order is its bucket order;
+ * slot order here depends on which lane won a claim inside an add and must
+ * not show).  On the device a hash with one object is copied by the
+ * workgroup; a hash with several is served by one lane, a chain walk per
+ * object and its bytes one by one: right for the rare equal 64-bit hashes,
+ * slow for a caller's own hash function that puts many or large objects under
+ * one hash.  A hash may repeat in the request: every copy sends its objects
+ * again.  d_parts[q] (nullable) is where hash q's first part begins and how
+ * many objects it sent; a returned hash without an object has its offset and
+ * objects = 0, a hash that was not returned {RAMCRC_READ_NONE, 0, 0}.
+ *
+ * Truncation (:258-263).  With start_q the offset at which hash q's parts
+ * begin and end_q the offset just past them, the reference keeps hash q
+ * exactly when start_q <= maxLength: it tests the length before the hash, so
+ * the reply may pass maxLength by one hash's parts.  The returned hashes are
+ * the leading ones with start_q <= max_length and, ours, end_q <=
+ * reply_capacity, since a reply buffer here does not grow; with
+ * reply_capacity >= max_length + the longest hash's parts the reference's
+ * rule alone decides.  max_length is the caller's maxResponseRpcLen -
+ * sizeof(ReadHashes::Response).  `hashes` is the number of returned hashes
+ * (respHdr->numHashes), reply_bytes the last returned end_q, `objects` what is
+ * in the reply.  objects_counted is `objects` plus the objects of the first
+ * hash not returned, if there is one: what the reference leaves in
+ * respHdr->numObjects, since :242 is not undone at :260; a caller sends the
+ * honest figure, `objects`.  All other counters cover returned hashes only.
+ * No byte of d_reply at or past reply_bytes is written.
+ *
+ * The tablet test of :218-226 (not owned, or locked for migration) is the
+ * caller's: it cuts the request before the first hash it does not own.
+ *
+ * n_hashes = 0 writes a zeroed summary and nothing else.  On a spoiled table
+ * d_reply and d_parts stay untouched, the summary is all zero with spoiled =
+ * 1, and no new refusal is raised: the lookup's rule.  No table word,
+ * descriptor, work array or batch counter is written: a call between two adds
+ * changes no later answer.
+ *
+ * RAMCRC_EINVAL before any launch: flags != 0; d_summary NULL; d_hashes NULL
+ * with n_hashes > 0; d_reply NULL with reply_capacity > 0; misaligned
+ * d_hashes, d_parts or d_summary (8); n_hashes >= 2^32 - 1.  d_reply needs no
+ * alignment and must not overlap any added batch's segments or another
+ * argument; the call cannot check this.  Data bytes are fetched as the
+ * aligned 16-byte words that hold at least one of them.
+ *
+ * Scratch comes from the context: 32 + 16 * ceil(n_hashes / 256) words and 6 *
+ * n_hashes entries.  After ramcrc_ctx_reserve(ctx, 32 + 16 * ceil(n / 256),
+ * 6 * n), or after any earlier call on the context that reserved as much, a
+ * call of up to n hashes does not allocate.  The call is stream-ordered,
+ * asynchronous and capturable and makes no host sync; lifetime and
+ * concurrency are the table's. */
+typedef struct ramcrc_hash_part {      /* one per asked hash; 16 bytes */
+    uint64_t off;                      /* where the hash's first object part begins in the reply;
+                                          RAMCRC_READ_NONE if the hash was not returned */
+    uint32_t objects;                  /* objects sent for this hash (0 is a returned, empty hash) */
+    uint32_t reserved;                 /* written as 0 */
+} ramcrc_hash_part;
+
+typedef struct ramcrc_read_hashes_summary {
+    uint64_t hashes;           /* respHdr->numHashes: the leading hashes answered */
+    uint64_t objects;          /* objects that are in the reply */
+    uint64_t objects_counted;  /* respHdr->numObjects as the reference computes it, see Truncation */
+    uint64_t reply_bytes;
+    uint64_t value_bytes, key_bytes;   /* PerfStats readObjectBytes / readKeyBytes of the objects in the reply */
+    uint64_t empty;            /* returned hashes with no object */
+    uint64_t tombstones;       /* keys of returned hashes that matched and whose winner is a tombstone */
+    uint64_t spoiled;
+} ramcrc_read_hashes_summary;
+
+int ramcrc_replay_table_read_hashes_device(ramcrc_replay_table* t, uint64_t table_id,
+                                           const uint64_t* d_hashes, uint64_t n_hashes,
+                                           uint32_t flags /* must be 0 */, void* d_reply,
+                                           uint64_t reply_capacity, uint64_t max_length,
+                                           ramcrc_hash_part* d_parts /* nullable */,
+                                           ramcrc_read_hashes_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_read_hashes_host(ramcrc_replay_table_host* t, uint64_t table_id,
+                                         const uint64_t* hashes, uint64_t n_hashes, uint32_t flags,
+                                         void* reply, uint64_t reply_capacity, uint64_t max_length,
+                                         ramcrc_hash_part* parts, ramcrc_read_hashes_summary* summary);
+
 /* A multi-write: the loop of MasterService::multiWrite
  * (src/MasterService.cc:1523-1601) over ObjectManager::writeObject
  * (src/ObjectManager.cc:1181-1350), against the replay table.  The call does

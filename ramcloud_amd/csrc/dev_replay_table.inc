@@ -144,13 +144,17 @@ __device__ __forceinline__ uint64_t rtab_rank(uint32_t type, uint32_t batch, uin
 }
 
 // The key of record j of batch b, which claimed a slot and so is a participant.
-__device__ __forceinline__ ResKey rtab_key_of(const RtabBatch& b, uint64_t j)
+__device__ __forceinline__ ResKey rtab_key_of_row(const RtabBatch& b, const u32x4 r)
 {
-    const u32x4 r = b.entries[j];
     const uint64_t pay = uint64_t(r.y) + 1 + ((r.w >> 6) & 3) + 1;
     const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
     const ramcrc_part::Parsed p = ramcrc_part::parse(r.w & 0x3f, r.z, true, rd);
     return ResKey{p.table_id, rd.pay + p.key_off, p.key_len};
+}
+
+__device__ __forceinline__ ResKey rtab_key_of(const RtabBatch& b, uint64_t j)
+{
+    return rtab_key_of_row(b, b.entries[j]);
 }
 
 // The version of record i of batch b, a participant.
@@ -510,6 +514,56 @@ struct LookHit {
     ramcrc_look::Value v;    // the value's place in it
 };
 
+// A slot's words decoded, for every walk over the table between adds (the
+// probe below, dev_read_hashes.inc).  The claimant of claim word c:
+__device__ __forceinline__ uint32_t rtab_claim_batch(uint64_t c)
+{
+    return uint32_t(c >> 32);
+}
+
+__device__ __forceinline__ uint64_t rtab_claim_record(uint64_t c)
+{
+    return (c & 0xFFFFFFFFull) - 1;
+}
+
+// The winner a nonzero pick word names, as rtab_winner decodes it.
+__device__ __forceinline__ bool rtab_pick_object(uint64_t pick)
+{
+    return (~pick >> 48) & 1;
+}
+
+__device__ __forceinline__ uint32_t rtab_pick_batch(uint64_t pick)
+{
+    return uint32_t(~pick >> 32) & 0xFFFFu;
+}
+
+__device__ __forceinline__ uint32_t rtab_pick_record(uint64_t pick)
+{
+    return uint32_t(~pick);
+}
+
+// The same with the winner's row and its payload.
+struct RtabWin {
+    uint32_t batch, record;
+    bool obj;
+    u32x4 row;      // {segment, offset, length, header}
+    uint32_t pay;   // the payload's offset in its segment
+    PartRd rd;
+};
+
+__device__ __forceinline__ RtabWin rtab_decode_pick(const RtabDesc& a, uint64_t pick)
+{
+    RtabWin w;
+    w.batch = rtab_pick_batch(pick);
+    w.record = rtab_pick_record(pick);
+    w.obj = rtab_pick_object(pick);
+    const RtabBatch& b = a.batches[w.batch];
+    w.row = b.entries[w.record];
+    w.pay = w.row.y + 1 + ((w.row.w >> 6) & 3) + 1;
+    w.rd = PartRd{b.base + uint64_t(w.row.x) * b.stride + w.pay};
+    return w;
+}
+
 // Query i's answer: the probe k_rtab_lookup and k_rtab_read_size share.
 template <bool kGiven>
 __device__ __forceinline__ ramcrc_lookup_result rtab_probe(const RtabDesc& a, const LookDesc& q,
@@ -535,27 +589,23 @@ __device__ __forceinline__ ramcrc_lookup_result rtab_probe(const RtabDesc& a, co
         const uint64_t c = *rtab_word(a, s, 2);
         if (c == 0)
             break;
-        const ResKey k = rtab_key_of(a.batches[c >> 32], (c & 0xFFFFFFFFull) - 1);
+        const ResKey k = rtab_key_of(a.batches[rtab_claim_batch(c)], rtab_claim_record(c));
         if (k.table_id != table_id || k.len != len || !res_bytes_equal(k.addr, addr, len))
             continue;
         const uint64_t pick = *rtab_word(a, s, 1);
         if (pick == 0)   // (between adds every claimed slot has one)
             break;
-        const uint64_t rank = ~pick;   // as rtab_winner decodes it
-        const uint32_t wb = uint32_t(rank >> 32) & 0xFFFFu, wr = uint32_t(rank);
-        const RtabBatch& b = a.batches[wb];
-        const u32x4 r = b.entries[wr];
-        const uint32_t pay = r.y + 1 + ((r.w >> 6) & 3) + 1;
-        const PartRd rd{b.base + uint64_t(r.x) * b.stride + pay};
-        res.ref = ramcrc_replay_ref{wb, wr};
-        res.version = ramcrc_res::version(r.w & 0x3f, rd);
-        if ((rank >> 48) & 1) {
-            const ramcrc_look::Value v = ramcrc_look::object_value(r.z, rd);
+        const RtabWin w = rtab_decode_pick(a, pick);
+        const u32x4 r = w.row;
+        res.ref = ramcrc_replay_ref{w.batch, w.record};
+        res.version = ramcrc_res::version(r.w & 0x3f, w.rd);
+        if (w.obj) {
+            const ramcrc_look::Value v = ramcrc_look::object_value(r.z, w.rd);
             res.kind = RAMCRC_LOOKUP_OBJECT;
             res.segment = r.x;
-            res.value_off = pay + v.off;
+            res.value_off = w.pay + v.off;
             res.value_len = v.len;
-            *hit = LookHit{rd.pay, r.z, v};
+            *hit = LookHit{w.rd.pay, r.z, v};
         } else {
             res.kind = RAMCRC_LOOKUP_TOMBSTONE;
         }

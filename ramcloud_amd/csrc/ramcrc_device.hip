@@ -63,6 +63,7 @@
 //   dev_resolve.inc  k_res_* (replayed objects and tombstones: newest wins)
 //   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table,
 //                         its lookup by key and a multi-read's reply)
+//   dev_read_hashes.inc   k_rh_* (an indexed read's reply: objects by primary-key hash)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -83,6 +84,7 @@
 #include "partition_rules.h"
 #include "lookup_rules.h"
 #include "read_rules.h"
+#include "read_hashes_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -112,6 +114,7 @@ using ramcrc::OpTable;
 #include "dev_partition.inc"
 #include "dev_resolve.inc"
 #include "dev_replay_table.inc"
+#include "dev_read_hashes.inc"
 #include "dev_write.inc"
 #include "dev_remove.inc"
 #include "dev_increment.inc"
@@ -1565,6 +1568,62 @@ int ramcrc_replay_table_read_device(ramcrc_replay_table* t, const void* d_keys, 
     HIPCHK(hipGetLastError());
     if (n_queries) {
         hipLaunchKernelGGL(k_rtab_read_gather, grid, dim3(kPartThreads), 0, s, a, q, r);
+        HIPCHK(hipGetLastError());
+    }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_read_hashes_device(ramcrc_replay_table* t, uint64_t table_id,
+                                           const uint64_t* d_hashes, uint64_t n_hashes, uint32_t flags,
+                                           void* d_reply, uint64_t reply_capacity, uint64_t max_length,
+                                           ramcrc_hash_part* d_parts, ramcrc_read_hashes_summary* d_summary,
+                                           void* stream)
+{
+    if (!t || flags != 0 || !d_summary || n_hashes >= 0xFFFFFFFFull || (n_hashes && !d_hashes) ||
+        (reply_capacity && !d_reply))
+        return RAMCRC_EINVAL;
+    const uint64_t R = reinterpret_cast<uint64_t>(d_reply);
+    if ((reinterpret_cast<uint64_t>(d_hashes) & 7) || (reinterpret_cast<uint64_t>(d_parts) & 7) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || R > UINT64_MAX - reply_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: a line for the scan's word to the gather, then the tile sums,
+    // in the chunk-partial buffer; the per-hash words in the plan buffer
+    // (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_hashes + kPartThreads - 1) / kPartThreads;
+    int rc = reserve_locked(c, kLookCountWords + 2 * kRhTileStride * ntiles, kRhRecWords * n_hashes);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    RhDesc r{};
+    r.table_id = table_id;
+    r.hashes = d_hashes;
+    r.nq = n_hashes;
+    r.reply = R;
+    r.cap = reply_capacity;
+    r.max_length = max_length;
+    r.parts = reinterpret_cast<uint64_t*>(d_parts);
+    r.summary = d_summary;
+    r.rec = c->plan_local;
+    r.head = reinterpret_cast<unsigned long long*>(c->partials);
+    r.tile = reinterpret_cast<uint64_t*>(c->partials + kLookCountWords);
+    const dim3 grid(rtab_grid(c, n_hashes, kPartThreads));
+    if (n_hashes) {
+        HIPCHK(hipMemsetAsync(r.tile, 0, kRhTileStride * ntiles * sizeof(uint64_t), s));
+        hipLaunchKernelGGL(k_rh_size, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rh_scan, dim3(1), dim3(kPartThreads), 0, s, a, r);
+    HIPCHK(hipGetLastError());
+    if (n_hashes) {
+        hipLaunchKernelGGL(k_rh_gather, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+        // (the hashes with several objects: nearly always a word a tile)
+        hipLaunchKernelGGL(k_rh_several, grid, dim3(kPartThreads), 0, s, a, r);
         HIPCHK(hipGetLastError());
     }
     return RAMCRC_OK;

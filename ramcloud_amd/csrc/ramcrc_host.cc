@@ -28,6 +28,7 @@
 #include "partition_rules.h"
 #include "lookup_rules.h"
 #include "read_rules.h"
+#include "read_hashes_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -697,6 +698,7 @@ struct ramcrc_replay_table_host {
         uint64_t stride;
         const ramcrc_seg_entry* entries;
         bool retired;          // cleaned out (ramcrc_replay_table_clean_host): nothing of it is read
+        const uint64_t* key_hash = nullptr;   // the caller's hashes; null: none (the survivor of a clean)
     };
     uint64_t key_cap = 0, keys = 0, safe_version = 0;
     uint32_t max_batches = 0;
@@ -769,6 +771,7 @@ int ramcrc_replay_table_add_host(ramcrc_replay_table_host* t, const void* base, 
     } catch (...) {
         return RAMCRC_ENOMEM;
     }
+    t->batches.back().key_hash = key_hash;
     if (batch)
         *batch = uint32_t(bno);
     if (t->spoiled)
@@ -1066,6 +1069,105 @@ int ramcrc_replay_table_read_host(ramcrc_replay_table_host* t, const void* keys,
             memcpy(reinterpret_cast<uint8_t*>(part_off) + i * 8, &at, 8);
     }
     *summary = sm;
+    return RAMCRC_OK;
+}
+
+// An indexed read's reply (the rules of read_hashes_rules.h): per asked hash
+// the chain from its home slot, the matching keys' object winners in the order
+// of their {batch, record}, the parts; the loop ends at the first hash that is
+// not returned.
+int ramcrc_replay_table_read_hashes_host(ramcrc_replay_table_host* t, uint64_t table_id,
+                                         const uint64_t* hashes, uint64_t n_hashes, uint32_t flags,
+                                         void* reply, uint64_t reply_capacity, uint64_t max_length,
+                                         ramcrc_hash_part* parts, ramcrc_read_hashes_summary* summary)
+{
+    namespace rh = ramcrc_rh;
+    if (!t || flags != 0 || !summary || n_hashes >= 0xFFFFFFFFull || (n_hashes && !hashes) ||
+        (reply_capacity && !reply))
+        return RAMCRC_EINVAL;
+    ramcrc_read_hashes_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+        return RAMCRC_OK;
+    }
+    struct Obj {
+        uint64_t order, version;
+        const uint8_t* data;
+        uint32_t len;
+    };
+    std::vector<Obj> objs;
+    const uint64_t mask = t->slots.size() - 1;
+    uint8_t* const out = static_cast<uint8_t*>(reply);
+    bool open = true;   // every hash so far was returned
+    try {
+        for (uint64_t q = 0; q < n_hashes; q++) {
+            uint64_t h;   // (no alignment rule)
+            memcpy(&h, reinterpret_cast<const uint8_t*>(hashes) + q * 8, 8);
+            rh::Found f = rh::nothing();
+            objs.clear();
+            uint64_t s = h & mask;
+            for (uint64_t step = 0; open && step <= mask; step++, s = (s + 1) & mask) {
+                const ramcrc_replay_table_host::Slot& sl = t->slots[s];
+                if (!sl.claim)
+                    break;
+                if (sl.table_id != table_id)
+                    continue;
+                const ramcrc_replay_table_host::Batch& cb = t->batches[sl.claim >> 32];
+                uint64_t rec_hash;   // the claimant's record hash
+                if (cb.key_hash)
+                    memcpy(&rec_hash, reinterpret_cast<const uint8_t*>(cb.key_hash) +
+                                          ((sl.claim & 0xFFFFFFFFull) - 1) * 8, 8);
+                else
+                    rec_hash = ramcrc::key_hash(sl.table_id, sl.key, sl.key_len);
+                if (rec_hash != h)
+                    continue;
+                if (!((sl.rank >> 48) & 1)) {
+                    f.tombstones++;
+                    continue;
+                }
+                const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
+                const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
+                ramcrc_seg_entry r;   // (a survivor's table has no alignment rule)
+                memcpy(&r, reinterpret_cast<const uint8_t*>(bt.entries) + uint64_t(wr) * sizeof(r), sizeof(r));
+                const uint32_t po = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+                const LookRd rd{bt.base + r.segment * bt.stride + po};
+                rh::add_object(&f, r.length, ramcrc_look::object_value(r.length, rd));
+                objs.push_back(Obj{rh::order_of(wb, wr), sl.version, rd.pay + rh::kObjHeader,
+                                   rh::data_len(r.length)});
+            }
+            ramcrc_hash_part part{RAMCRC_READ_NONE, 0u, 0u};
+            if (open && rh::returned(sm.reply_bytes, sm.reply_bytes + f.bytes, max_length, reply_capacity)) {
+                // one hash's objects: ascending {batch, record} (insertion sort:
+                // more than one needs equal 64-bit hashes)
+                for (size_t i = 1; i < objs.size(); i++)
+                    for (size_t j = i; j > 0 && objs[j].order < objs[j - 1].order; j--)
+                        std::swap(objs[j], objs[j - 1]);
+                part.off = sm.reply_bytes;
+                part.objects = uint32_t(f.objects);
+                uint64_t at = sm.reply_bytes;
+                for (const Obj& o : objs) {
+                    for (uint32_t b = 0; b < rh::kPartHeader; b++)
+                        out[at + b] = rh::header_byte(o.version, o.len, b);
+                    if (o.len)
+                        memcpy(out + at + rh::kPartHeader, o.data, o.len);
+                    at += rh::kPartHeader + o.len;
+                }
+                rh::count_returned(&sm, f);
+            } else if (open) {
+                // the first hash that is not returned: its objects stay counted
+                // in the reference's numObjects (:242 is not undone at :260)
+                sm.objects_counted = f.objects;
+                open = false;
+            }
+            if (parts)
+                memcpy(reinterpret_cast<uint8_t*>(parts) + q * sizeof(part), &part, sizeof(part));
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.objects_counted += sm.objects;
+    memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
     return RAMCRC_OK;
 }
 

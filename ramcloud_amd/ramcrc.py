@@ -125,6 +125,8 @@ def lib():
                                                   vp, vp]),
         "ramcrc_replay_table_read_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp,
                                                 vp]),
+        "ramcrc_replay_table_read_hashes_device": (i32, [vp, u64, vp, u64, u32, vp, u64, u64, vp, vp, vp]),
+        "ramcrc_replay_table_read_hashes_host": (i32, [vp, u64, vp, u64, u32, vp, u64, u64, vp, vp]),
         "ramcrc_replay_table_write_device": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                    vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_write_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
@@ -573,6 +575,36 @@ class ReplayTableHost:
             p(summary))
         _check(rc, "ramcrc_replay_table_read_host")
         return reply[:int(summary[0]["reply_bytes"])], part_off, summary[0], results
+
+    def read_hashes(self, table_id, hashes, max_length, reply_capacity=None):
+        """An indexed read's reply (ramcrc_replay_table_read_hashes_host): for
+        every asked primary-key hash the objects of table_id whose record hash
+        equals it.  hashes: uint64 [n]; max_length: the reference's maxLength;
+        reply_capacity: the reply buffer's size, default: room for max_length
+        and one hash's overshoot.  Returns (reply: uint8 [reply_bytes], parts:
+        segments.HASH_PART_DTYPE [n], summary: a
+        segments.READ_HASHES_SUMMARY_DTYPE scalar);
+        segments.read_hashes_objects splits the reply.  On a spoiled table the
+        reply is empty, parts are the wrapper's zeros and summary["spoiled"]
+        is 1."""
+        from . import segments as _seg
+        hashes = np.ascontiguousarray(hashes, np.uint64).reshape(-1)
+        n = hashes.shape[0]
+        # no reply is longer than every held object sent for every hash, 12
+        # bytes and at most the payload each
+        held = sum(int(k[2][:, 2].sum()) + 12 * k[2].shape[0] for k in self._keep if k is not None)
+        if reply_capacity is None:
+            reply_capacity = min(int(max_length), n * held) + held
+        room = min(int(reply_capacity), n * held)
+        reply = np.zeros(room, np.uint8)
+        parts = np.zeros(n, _seg.HASH_PART_DTYPE)
+        summary = np.zeros(1, _seg.READ_HASHES_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_read_hashes_host(
+            self._h, int(table_id), p(hashes), n, 0, p(reply), room, int(max_length), p(parts),
+            p(summary))
+        _check(rc, "ramcrc_replay_table_read_hashes_host")
+        return reply[:int(summary[0]["reply_bytes"])], parts, summary[0]
 
     def write(self, data, reqs, out_capacity, next_version, timestamp=0, rules=None,
               key_hash=None, batch_segment_id=None, want_refs=True, want_old=False):
@@ -1245,6 +1277,39 @@ class ReplayTable:
             1 if value_only else 0, _ptr(reply) if reply_cap else None, int(reply_cap),
             _ptr(part_off), _ptr(results), _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_read_device")
+        return reply
+
+    def read_hashes(self, table_id, hashes, reply, summary, max_length, parts=None, n_hashes=None,
+                    reply_capacity=None, stream=None):
+        """An indexed read's reply, packed on the device
+        (ramcrc_replay_table_read_hashes_device): for every asked primary-key
+        hash the objects of table_id whose record hash equals it.  hashes:
+        int64 CUDA [n] (n_hashes default: hashes.numel()); reply: uint8 CUDA
+        out, any alignment (reply_capacity: its size in bytes, default
+        reply.numel()); max_length: the reference's maxLength, which the reply
+        may pass by one hash's parts; summary: int64 CUDA [9] out
+        (segments.READ_HASHES_SUMMARY_DTYPE); parts: CUDA out, 16 bytes a hash
+        (segments.HASH_PART_DTYPE), 8-byte aligned, or None.  The reply must
+        not overlap an added batch.  Read-only on the table.  Asynchronous;
+        segments.read_hashes_objects splits the reply on the host."""
+        if n_hashes is None:
+            n_hashes = 0 if hashes is None else hashes.numel()
+        if reply_capacity is None:
+            reply_capacity = 0 if reply is None else reply.numel() * reply.element_size()
+        nbytes = lambda x: x.numel() * x.element_size()
+        if reply_capacity and (reply is None or nbytes(reply) < reply_capacity):
+            raise RamcrcError("ReplayTable.read_hashes: reply is smaller than reply_capacity")
+        if n_hashes and (hashes is None or nbytes(hashes) < 8 * n_hashes):
+            raise RamcrcError("ReplayTable.read_hashes: fewer hashes than n_hashes")
+        if parts is not None and nbytes(parts) < 16 * n_hashes:
+            raise RamcrcError("ReplayTable.read_hashes: parts is smaller than the hashes")
+        if summary is None or nbytes(summary) < 72:
+            raise RamcrcError("ReplayTable.read_hashes: summary is smaller than 72 bytes")
+        rc = lib().ramcrc_replay_table_read_hashes_device(
+            self._h, int(table_id), _ptr(hashes) if n_hashes else None, int(n_hashes), 0,
+            _ptr(reply) if reply_capacity else None, int(reply_capacity), int(max_length),
+            _ptr(parts), _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_read_hashes_device")
         return reply
 
     def write(self, data, reqs, out, out_cert, parts, summary, next_version, timestamp=0,

@@ -77,6 +77,14 @@ READ_VALUE_ONLY = 1
 READ_NONE = 0xFFFFFFFFFFFFFFFF
 STATUS_OK, STATUS_OBJECT_DOESNT_EXIST, STATUS_OBJECT_EXISTS = 0, 3, 4
 STATUS_WRONG_VERSION, STATUS_REQUEST_FORMAT_ERROR = 5, 9
+# ramcrc_hash_part, ramcrc_read_hashes_summary and the packed header of an
+# object part (ramcrc_replay_table_read_hashes_device / _host); a hash that was
+# not returned has off = READ_NONE
+HASH_PART_DTYPE = np.dtype([("off", "<u8"), ("objects", "<u4"), ("reserved", "<u4")])
+READ_HASHES_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "hashes", "objects", "objects_counted", "reply_bytes", "value_bytes", "key_bytes", "empty",
+    "tombstones", "spoiled")])
+READ_HASHES_OBJECT_DTYPE = np.dtype([("version", "<u8"), ("length", "<u4")])   # packed
 # ramcrc_write_req, ramcrc_write_ref, ramcrc_write_summary, the packed
 # MultiOp::Response::WritePart and ramcrc_seg_cert
 # (ramcrc_replay_table_write_device / _host)
@@ -250,6 +258,25 @@ def multi_read_parts(reply, returned):
             raise ValueError("multi_read_parts: the reply ends inside a part's data")
         out.append((status, version, raw[at:at + n]))
         at += n
+    return out
+
+
+def read_hashes_objects(reply, objects):
+    """The first `objects` object parts of an indexed read's reply (bytes or a
+    uint8 array) as (version, keys-and-value bytes): a packed 12-byte
+    READ_HASHES_OBJECT_DTYPE header each, followed by `length` bytes."""
+    raw = np.ascontiguousarray(reply, np.uint8).reshape(-1).tobytes() \
+        if not isinstance(reply, (bytes, bytearray)) else bytes(reply)
+    out, at = [], 0
+    for _ in range(int(objects)):
+        if at + 12 > len(raw):
+            raise ValueError("read_hashes_objects: the reply ends inside a header")
+        version, length = (int(x) for x in np.frombuffer(raw, READ_HASHES_OBJECT_DTYPE, 1, at)[0])
+        at += 12
+        if at + length > len(raw):
+            raise ValueError("read_hashes_objects: the reply ends inside an object")
+        out.append((version, raw[at:at + length]))
+        at += length
     return out
 
 
