@@ -451,6 +451,33 @@ class ReplayTable {
               "ramcrc_replay_table_read_hashes_device");
     }
 
+    /// One reply of MasterService::enumerate (src/MasterService.cc:409-456)
+    /// over Enumeration::complete (src/Enumeration.cc:269-351), packed on the
+    /// device: the objects of tableId whose key hash lies in [firstHash,
+    /// lastHash] (requestedTabletStartHash, the top frame's tabletEndHash) and
+    /// that none of the nStale stale frames (host memory, read before the call
+    /// returns) hides, bucket by bucket from the top frame's cursor
+    /// (bucketIndex, bucketNextHash) up to bucketLimit (0: the whole table), as
+    /// {u32 length, log entry} entries that end within maxBytes
+    /// (maxPayloadBytes less what the reply already holds) and
+    /// payloadCapacity; with keysOnly an entry ends before its value.
+    /// d_summary->num_buckets, next_bucket and next_hash are the top frame to
+    /// serialise; when next_bucket == num_buckets with nothing sent the caller
+    /// pops frames and returns tabletEndHash + 1.  Read-only on the table;
+    /// d_payload must not overlap an added batch.
+    void
+    enumerate(uint64_t tableId, uint64_t firstHash, uint64_t lastHash, uint64_t bucketIndex,
+              uint64_t bucketNextHash, uint64_t bucketLimit, const ramcrc_enum_frame* stale,
+              uint32_t nStale, bool keysOnly, void* d_payload, uint64_t payloadCapacity,
+              uint64_t maxBytes, ramcrc_enumerate_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_enumerate_device(table, tableId, firstHash, lastHash, bucketIndex,
+                                                   bucketNextHash, bucketLimit, stale, nStale,
+                                                   keysOnly ? RAMCRC_ENUM_KEYS_ONLY : 0u, d_payload,
+                                                   payloadCapacity, maxBytes, d_summary, stream),
+              "ramcrc_replay_table_enumerate_device");
+    }
+
     /// MasterService::multiWrite (src/MasterService.cc:1523-1601) for nReqs
     /// keysAndValue images, on the device: per request the lookup above, the
     /// RejectRules, the new version as ObjectManager::writeObject chooses it

@@ -1020,6 +1020,136 @@ int ramcrc_replay_table_read_hashes_host(ramcrc_replay_table_host* t, uint64_t t
                                          void* reply, uint64_t reply_capacity, uint64_t max_length,
                                          ramcrc_hash_part* parts, ramcrc_read_hashes_summary* summary);
 
+/* One reply of a table enumeration: MasterService::enumerate
+ * (src/MasterService.cc:409-456) over Enumeration::complete
+ * (src/Enumeration.cc:269-351), against the replay table.  The call walks the
+ * table's buckets from a cursor, selects the keys of one table id and tablet
+ * hash range that no stale iterator frame hides, and packs {u32 length,
+ * object} entries into d_payload until a byte limit or a bucket limit; the
+ * summary carries the cursor to go on with.  No key and no hash is given: this
+ * is the one call that walks the table instead of probing it.  Rules marked
+ * "ours" cover what the reference leaves open or where this form differs.
+ *
+ * Buckets.  The table has S = slots buckets (summary.num_buckets); a key's
+ * bucket is its home, hash & (S - 1), never the slot the key happens to lie
+ * in.  This is HashTable::findBucketIndex (src/HashTable.cc:489-495) for S <
+ * 2^48, which every table here is, so a frame written from this call's cursor
+ * means the same to the reference's stale-frame filter.  The hash is the
+ * record hash exactly as the read-hashes call defines it: d_key_hash[record]
+ * of the claimant's batch when that was added with hashes, Key::getHash of the
+ * claimant's key, computed in the call, otherwise; the same caveat for cleaned
+ * tables applies.  The keys of bucket b lie on the chain from slot b to the
+ * first unclaimed slot (slots are never un-claimed), which the call walks, at
+ * most every slot once.  Slot order must not show: the payload is defined by
+ * hashes and winners only.
+ *
+ * Selection (enumerateBucket, :58-108).  A claimed slot with record hash h is
+ * selected when its claimant's table id equals table_id -- ours: all 64 bits
+ * --, first_hash <= h <= last_hash, no stale frame hides it, and, for bucket
+ * bucket_index only, h >= bucket_next_hash.  Stale frame f (any power-of-two
+ * f.num_buckets, not necessarily S) hides h when f.tablet_start_hash <= h <=
+ * f.tablet_end_hash and, with idx = (h & 0xffffffffffff) & (f.num_buckets -
+ * 1), either idx < f.bucket_index or idx == f.bucket_index && h <
+ * f.bucket_next_hash (:80-100).  A selected key whose winner is a tombstone
+ * sends nothing (:67); one whose winner is an object sends one entry.  Ours:
+ * the reference applies top().bucketNextHash to every later bucket as well
+ * and never clears it (:103, :330), which loses keys after a bucket larger
+ * than a whole reply; here it holds for the cursor's bucket alone and
+ * next_hash is 0 once that bucket is finished.  The two agree unless one
+ * bucket alone exceeds max_bytes.  first_hash > last_hash selects nothing.
+ *
+ * Entry (appendObjectsToBuffer, :128-154).  A u32 little-endian `length`, then
+ * `length` bytes of the winner's payload from byte 0, header and checksum
+ * included, as log.getEntry gives them.  With RAMCRC_ENUM_KEYS_ONLY `length`
+ * is the offset of the value, so the entry ends before it; for an object
+ * whose keys run past its payload that offset is the payload length.  Entries
+ * lie back to back from d_payload + 0, so one may begin at any byte.
+ *
+ * Order.  Ascending bucket; within a bucket ascending {hash, winner batch,
+ * winner record}.  Ours: the reference's order within a bucket is its cache
+ * lines', except where it must cut a bucket, which it then sorts by hash
+ * (:319-320); always sorting makes its two cases one.
+ *
+ * Cut.  lim = min(max_bytes, payload_capacity); max_bytes is the caller's
+ * maxPayloadBytes less what the reply already holds.  A bucket is kept whole
+ * when its last entry ends at or before lim (:145, :302-313).  The first
+ * bucket that is not: when it is a later bucket of the call it is left out,
+ * next_bucket names it and next_hash = 0; when it is bucket_index itself
+ * (:318-332) its leading entries that end at or before lim are sent and
+ * next_hash is the hash of the first entry not sent -- ours: the cut moves
+ * back to before the first entry that has that hash, so a resume with h >=
+ * next_hash sends nothing twice; if that leaves nothing, stuck = 1 (the
+ * reference loops forever here) and the caller must offer more room.  Either
+ * way full = 1.  With every bucket below the limit kept, next_bucket is that
+ * limit, next_hash = 0 and full = 0.  Ours: bucket_limit (0: S).  The
+ * reference scans until the reply is full or the table ends, a reply's worth
+ * of work there and a pass over the rest of the table here; the caller bounds
+ * the pass instead, and a reply cut short by bucket_limit is a legal
+ * enumeration reply.  No byte at or past payload_bytes is written.  What to
+ * do when next_bucket == num_buckets stays with the caller, with the
+ * iterator's serialisation: pop frames, return tabletEndHash + 1 (:338-350).
+ *
+ * Summary.  objects, payload_bytes, value_bytes and key_bytes cover the
+ * entries sent; value and key bytes are the objects' as the read counts them,
+ * whatever the flags.  tombstones counts the selected keys of the buckets kept
+ * whole whose winner is a tombstone.
+ *
+ * The call changes no table word, descriptor, work array or batch counter.  On
+ * a spoiled table d_payload stays untouched and the summary is all zero with
+ * spoiled = 1: the lookup's rule.
+ *
+ * RAMCRC_EINVAL before any launch: unknown flag bits; d_summary NULL or
+ * misaligned (8); d_payload NULL with payload_capacity > 0; bucket_index > S;
+ * bucket_limit not 0 and below bucket_index or above S; n_stale >
+ * RAMCRC_ENUM_MAX_STALE; stale NULL with n_stale > 0; a stale frame whose
+ * num_buckets is 0 or no power of two.  `stale` is host memory, read before
+ * the call returns and carried in the launch descriptor.  d_payload needs no
+ * alignment and must not overlap any added batch's segments; data bytes are
+ * fetched as the aligned 16-byte words that hold at least one of them.
+ *
+ * Scratch comes from the context and grows with the buckets' tiles, not with
+ * buckets or objects: 32 + 16 * ceil(n / 256) words for the n = bucket_limit -
+ * bucket_index buckets of the call, no entries.  After ramcrc_ctx_reserve(ctx,
+ * 32 + 16 * ceil(S / 256), 0), or after any earlier call on the context that
+ * reserved as much, no call on the table allocates.  The price is a second
+ * chain walk when the entries are copied.  The call is stream-ordered,
+ * asynchronous and capturable and makes no host sync; lifetime and
+ * concurrency are the table's. */
+typedef struct ramcrc_enum_frame {      /* EnumerationIterator::Frame, 40 bytes */
+    uint64_t tablet_start_hash, tablet_end_hash, num_buckets, bucket_index, bucket_next_hash;
+} ramcrc_enum_frame;
+#define RAMCRC_ENUM_KEYS_ONLY 1u
+#define RAMCRC_ENUM_MAX_STALE 8u
+
+typedef struct ramcrc_enumerate_summary {
+    uint64_t num_buckets;      /* S, the table's slots: Frame::numBuckets of this table */
+    uint64_t next_bucket;      /* Frame::bucketIndex to go on with */
+    uint64_t next_hash;        /* Frame::bucketNextHash to go on with; 0 unless next_bucket was sent in part */
+    uint64_t objects, payload_bytes;
+    uint64_t value_bytes, key_bytes;   /* of the objects sent, counted as the read counts them */
+    uint64_t tombstones;       /* selected keys of finished buckets whose winner is a tombstone */
+    uint64_t full;             /* 1: a bucket below bucket_limit was cut or left out */
+    uint64_t stuck;            /* 1: full, and nothing was sent: the first object alone does not fit */
+    uint64_t spoiled;
+} ramcrc_enumerate_summary;
+
+int ramcrc_replay_table_enumerate_device(ramcrc_replay_table* t, uint64_t table_id,
+        uint64_t first_hash, uint64_t last_hash,          /* requestedTabletStartHash, top().tabletEndHash */
+        uint64_t bucket_index, uint64_t bucket_next_hash, /* the top frame's cursor */
+        uint64_t bucket_limit,                            /* 0: S */
+        const ramcrc_enum_frame* stale /* host */, uint32_t n_stale,
+        uint32_t flags, void* d_payload, uint64_t payload_capacity, uint64_t max_bytes,
+        ramcrc_enumerate_summary* d_summary, void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes.  Returns RAMCRC_OK on a spoiled table, with the outputs
+ * described above. */
+int ramcrc_replay_table_enumerate_host(ramcrc_replay_table_host* t, uint64_t table_id,
+        uint64_t first_hash, uint64_t last_hash, uint64_t bucket_index, uint64_t bucket_next_hash,
+        uint64_t bucket_limit, const ramcrc_enum_frame* stale, uint32_t n_stale, uint32_t flags,
+        void* payload, uint64_t payload_capacity, uint64_t max_bytes,
+        ramcrc_enumerate_summary* summary);
+
 /* A multi-write: the loop of MasterService::multiWrite
  * (src/MasterService.cc:1523-1601) over ObjectManager::writeObject
  * (src/ObjectManager.cc:1181-1350), against the replay table.  The call does

@@ -62,8 +62,13 @@ struct RhDesc {
     unsigned long long* head;       // scratch line: [0] the returned hashes, written by the scan
 };
 
-// Does the slot claimed by c hold a key of table_id whose record hash is h?
-__device__ __forceinline__ bool rh_matches(const RtabDesc& a, uint64_t table_id, uint64_t h, uint64_t c)
+// Does the slot claimed by c hold a key of table_id whose record hash is
+// wanted?  *hash: the record hash, where the answer is yes.  The decoding and
+// the record-hash test of every walk that goes by hashes (the one below,
+// dev_enumerate.inc); `wanted` is the walk's own test of the hash.
+template <typename Wanted>
+__device__ __forceinline__ bool rh_claimant(const RtabDesc& a, uint64_t table_id, uint64_t c,
+                                            const Wanted& wanted, uint64_t* hash)
 {
     const RtabBatch& b = a.batches[rtab_claim_batch(c)];
     const uint64_t j = rtab_claim_record(c);
@@ -76,12 +81,28 @@ __device__ __forceinline__ bool rh_matches(const RtabDesc& a, uint64_t table_id,
         // behind the branch on the hash, where it would wait for it.
         const u32x4 row = b.entries[j];
         const uint64_t kh = b.key_hash[j];
-        if ((kh != h) | (row.z == 0))
+        if (!wanted(kh) | (row.z == 0))
             return false;
+        *hash = kh;
         return rtab_key_of_row(b, row).table_id == table_id;
     }
     const ResKey k = rtab_key_of(b, j);
-    return k.table_id == table_id && part_key_hash(k.table_id, k.addr, k.len) == h;
+    if (k.table_id != table_id)
+        return false;
+    *hash = part_key_hash(k.table_id, k.addr, k.len);
+    return wanted(*hash);
+}
+
+struct RhIs {
+    uint64_t h;
+    __device__ __forceinline__ bool operator()(uint64_t kh) const { return kh == h; }
+};
+
+// The same for one asked hash h.
+__device__ __forceinline__ bool rh_matches(const RtabDesc& a, uint64_t table_id, uint64_t h, uint64_t c)
+{
+    uint64_t kh;
+    return rh_claimant(a, table_id, c, RhIs{h}, &kh);
 }
 
 // What hash h finds on its chain; *src and *version: of the last object met

@@ -64,6 +64,7 @@
 //   dev_replay_table.inc  k_rtab_* (newest wins across batches: the persistent table,
 //                         its lookup by key and a multi-read's reply)
 //   dev_read_hashes.inc   k_rh_* (an indexed read's reply: objects by primary-key hash)
+//   dev_enumerate.inc     k_en_* (one reply of a table enumeration: a walk over the buckets)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -85,6 +86,7 @@
 #include "lookup_rules.h"
 #include "read_rules.h"
 #include "read_hashes_rules.h"
+#include "enumerate_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -115,6 +117,7 @@ using ramcrc::OpTable;
 #include "dev_resolve.inc"
 #include "dev_replay_table.inc"
 #include "dev_read_hashes.inc"
+#include "dev_enumerate.inc"
 #include "dev_write.inc"
 #include "dev_remove.inc"
 #include "dev_increment.inc"
@@ -1624,6 +1627,73 @@ int ramcrc_replay_table_read_hashes_device(ramcrc_replay_table* t, uint64_t tabl
         HIPCHK(hipGetLastError());
         // (the hashes with several objects: nearly always a word a tile)
         hipLaunchKernelGGL(k_rh_several, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+    }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_enumerate_device(ramcrc_replay_table* t, uint64_t table_id, uint64_t first_hash,
+                                         uint64_t last_hash, uint64_t bucket_index,
+                                         uint64_t bucket_next_hash, uint64_t bucket_limit,
+                                         const ramcrc_enum_frame* stale, uint32_t n_stale, uint32_t flags,
+                                         void* d_payload, uint64_t payload_capacity, uint64_t max_bytes,
+                                         ramcrc_enumerate_summary* d_summary, void* stream)
+{
+    namespace en = ramcrc_en;
+    if (!t || (flags & ~RAMCRC_ENUM_KEYS_ONLY) || !d_summary || (payload_capacity && !d_payload) ||
+        n_stale > RAMCRC_ENUM_MAX_STALE || (n_stale && !stale))
+        return RAMCRC_EINVAL;
+    const uint64_t P = reinterpret_cast<uint64_t>(d_payload);
+    if ((reinterpret_cast<uint64_t>(d_summary) & 7) || P > UINT64_MAX - payload_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    const uint64_t S = t->nslots;
+    if (bucket_index > S || (bucket_limit && (bucket_limit < bucket_index || bucket_limit > S)))
+        return RAMCRC_EINVAL;
+    EnDesc r{};
+    // the stale frames travel in the launch descriptor: no copy to order, and
+    // the caller's array is free when the call returns
+    for (uint32_t k = 0; k < n_stale; k++) {
+        memcpy(&r.sel.stale[k], reinterpret_cast<const uint8_t*>(stale) + k * sizeof(*stale), sizeof(*stale));
+        if (en::bad_frame(r.sel.stale[k]))
+            return RAMCRC_EINVAL;
+    }
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: a line for the scan's words to the gather, then the tile sums,
+    // in the chunk-partial buffer; nothing per bucket (ramcrc.h states this
+    // size)
+    const uint64_t nb = (bucket_limit ? bucket_limit : S) - bucket_index;
+    const uint64_t ntiles = (nb + kPartThreads - 1) / kPartThreads;
+    int rc = reserve_locked(c, kLookCountWords + 2 * kEnTileStride * ntiles, 0);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    r.table_id = table_id;
+    r.nb = nb;
+    r.payload = P;
+    r.lim = en::limit(max_bytes, payload_capacity);
+    r.summary = d_summary;
+    r.flags = flags;
+    r.sel.first_hash = first_hash;
+    r.sel.last_hash = last_hash;
+    r.sel.bucket_index = bucket_index;
+    r.sel.bucket_next_hash = bucket_next_hash;
+    r.sel.n_stale = n_stale;
+    r.head = reinterpret_cast<unsigned long long*>(c->partials);
+    r.tile = reinterpret_cast<uint64_t*>(c->partials + kLookCountWords);
+    const dim3 grid(rtab_grid(c, nb, kPartThreads));
+    if (nb) {
+        HIPCHK(hipMemsetAsync(r.tile, 0, kEnTileStride * ntiles * sizeof(uint64_t), s));
+        hipLaunchKernelGGL(k_en_size, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_en_scan, dim3(1), dim3(kPartThreads), 0, s, a, r);
+    HIPCHK(hipGetLastError());
+    if (nb) {
+        hipLaunchKernelGGL(k_en_gather, grid, dim3(kPartThreads), 0, s, a, r);
         HIPCHK(hipGetLastError());
     }
     return RAMCRC_OK;

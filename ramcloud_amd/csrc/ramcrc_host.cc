@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <string>
 #include <unordered_set>
@@ -29,6 +30,7 @@
 #include "lookup_rules.h"
 #include "read_rules.h"
 #include "read_hashes_rules.h"
+#include "enumerate_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -1167,6 +1169,129 @@ int ramcrc_replay_table_read_hashes_host(ramcrc_replay_table_host* t, uint64_t t
         return RAMCRC_ENOMEM;
     }
     sm.objects_counted += sm.objects;
+    memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+    return RAMCRC_OK;
+}
+
+// One reply of an enumeration (the rules of enumerate_rules.h): bucket by
+// bucket from the cursor the chain from the bucket's slot, the selected keys
+// whose home the bucket is, their object winners in the order of {hash, batch,
+// record}; the loop ends at the first bucket that is not kept whole.
+int ramcrc_replay_table_enumerate_host(ramcrc_replay_table_host* t, uint64_t table_id,
+                                       uint64_t first_hash, uint64_t last_hash, uint64_t bucket_index,
+                                       uint64_t bucket_next_hash, uint64_t bucket_limit,
+                                       const ramcrc_enum_frame* stale, uint32_t n_stale, uint32_t flags,
+                                       void* payload, uint64_t payload_capacity, uint64_t max_bytes,
+                                       ramcrc_enumerate_summary* summary)
+{
+    namespace en = ramcrc_en;
+    if (!t || (flags & ~RAMCRC_ENUM_KEYS_ONLY) || !summary || (payload_capacity && !payload) ||
+        n_stale > RAMCRC_ENUM_MAX_STALE || (n_stale && !stale))
+        return RAMCRC_EINVAL;
+    const uint64_t S = t->slots.size();
+    if (bucket_index > S || (bucket_limit && (bucket_limit < bucket_index || bucket_limit > S)))
+        return RAMCRC_EINVAL;
+    en::Select sel{};
+    sel.first_hash = first_hash;
+    sel.last_hash = last_hash;
+    sel.bucket_index = bucket_index;
+    sel.bucket_next_hash = bucket_next_hash;
+    sel.n_stale = n_stale;
+    for (uint32_t k = 0; k < n_stale; k++) {
+        memcpy(&sel.stale[k], reinterpret_cast<const uint8_t*>(stale) + k * sizeof(*stale), sizeof(*stale));
+        if (en::bad_frame(sel.stale[k]))
+            return RAMCRC_EINVAL;
+    }
+    ramcrc_enumerate_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+        return RAMCRC_OK;
+    }
+    struct Ent {
+        uint64_t hash, order;
+        const uint8_t* pay;
+        uint32_t len;
+        ramcrc_look::Value v;
+    };
+    std::vector<Ent> ents;
+    const uint64_t mask = S - 1, lim = en::limit(max_bytes, payload_capacity);
+    const uint64_t end = bucket_limit ? bucket_limit : S;
+    uint8_t* const out = static_cast<uint8_t*>(payload);
+    en::Found all = en::nothing();   // what is sent
+    const auto send = [&](const Ent& e) {
+        const uint32_t length = en::entry_length(flags, e.len, e.v);
+        for (uint32_t b = 0; b < en::kLengthBytes; b++)
+            out[all.bytes + b] = en::length_byte(length, b);
+        memcpy(out + all.bytes + en::kLengthBytes, e.pay, length);
+        en::add_object(&all, flags, e.len, e.v);
+    };
+    sm.num_buckets = S;
+    sm.next_bucket = end;
+    try {
+        for (uint64_t b = bucket_index; b < end; b++) {
+            ents.clear();
+            en::Found f = en::nothing();
+            uint64_t s = b;
+            for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+                const ramcrc_replay_table_host::Slot& sl = t->slots[s];
+                if (!sl.claim)
+                    break;
+                if (sl.table_id != table_id)
+                    continue;
+                const ramcrc_replay_table_host::Batch& cb = t->batches[sl.claim >> 32];
+                uint64_t h;   // the claimant's record hash
+                if (cb.key_hash)
+                    memcpy(&h, reinterpret_cast<const uint8_t*>(cb.key_hash) +
+                                   ((sl.claim & 0xFFFFFFFFull) - 1) * 8, 8);
+                else
+                    h = ramcrc::key_hash(sl.table_id, sl.key, sl.key_len);
+                if ((h & mask) != b || !en::selected(sel, b, h))
+                    continue;
+                if (!((sl.rank >> 48) & 1)) {
+                    f.tombstones++;
+                    continue;
+                }
+                const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
+                const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
+                ramcrc_seg_entry r;   // (a survivor's table has no alignment rule)
+                memcpy(&r, reinterpret_cast<const uint8_t*>(bt.entries) + uint64_t(wr) * sizeof(r), sizeof(r));
+                const uint32_t po = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+                const LookRd rd{bt.base + r.segment * bt.stride + po};
+                const ramcrc_look::Value v = ramcrc_look::object_value(r.length, rd);
+                en::add_object(&f, flags, r.length, v);
+                ents.push_back(Ent{h, en::order_of(wb, wr), rd.pay, r.length, v});
+            }
+            std::sort(ents.begin(), ents.end(), [](const Ent& x, const Ent& y) {
+                return en::below(x.hash, x.order, y.hash, y.order);
+            });
+            if (all.bytes + f.bytes <= lim) {   // kept whole
+                for (const Ent& e : ents)
+                    send(e);
+                sm.tombstones += f.tombstones;
+                continue;
+            }
+            sm.full = 1;
+            sm.next_bucket = b;
+            if (b == bucket_index) {   // (nothing was sent before it)
+                en::Cut c = en::cut_begin();
+                for (const Ent& e : ents)
+                    if (!en::cut_entry(&c, lim, e.hash, flags, e.len, e.v))
+                        break;
+                sm.next_hash = c.next_hash;
+                for (uint64_t k = 0; k < c.sent.objects; k++)
+                    send(ents[k]);
+                sm.stuck = c.sent.objects == 0;
+            }
+            break;
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.objects = all.objects;
+    sm.payload_bytes = all.bytes;
+    sm.value_bytes = all.value_bytes;
+    sm.key_bytes = all.key_bytes;
     memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
     return RAMCRC_OK;
 }

@@ -127,6 +127,10 @@ def lib():
                                                 vp]),
         "ramcrc_replay_table_read_hashes_device": (i32, [vp, u64, vp, u64, u32, vp, u64, u64, vp, vp, vp]),
         "ramcrc_replay_table_read_hashes_host": (i32, [vp, u64, vp, u64, u32, vp, u64, u64, vp, vp]),
+        "ramcrc_replay_table_enumerate_device": (i32, [vp, u64, u64, u64, u64, u64, u64, vp, u32, u32, vp, u64,
+                                                       u64, vp, vp]),
+        "ramcrc_replay_table_enumerate_host": (i32, [vp, u64, u64, u64, u64, u64, u64, vp, u32, u32, vp, u64,
+                                                     u64, vp]),
         "ramcrc_replay_table_write_device": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                    vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_write_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
@@ -605,6 +609,42 @@ class ReplayTableHost:
             p(summary))
         _check(rc, "ramcrc_replay_table_read_hashes_host")
         return reply[:int(summary[0]["reply_bytes"])], parts, summary[0]
+
+    def enumerate(self, table_id, max_bytes, first_hash=0, last_hash=0xFFFFFFFFFFFFFFFF, bucket_index=0,
+                  bucket_next_hash=0, bucket_limit=0, stale=None, keys_only=False, payload_capacity=None):
+        """One reply of a table enumeration (ramcrc_replay_table_enumerate_host):
+        the objects of table_id with first_hash <= hash <= last_hash, bucket by
+        bucket from the cursor (bucket_index, bucket_next_hash) up to
+        bucket_limit (0: every bucket), as {u32 length, log entry} entries
+        that end within max_bytes.  stale: the iterator's stale frames
+        (segments.enum_frames or its rows); keys_only: entries end before the
+        value; payload_capacity: the payload buffer's size, default: room for
+        max_bytes.  Returns (payload: uint8 [payload_bytes], summary: a
+        segments.ENUMERATE_SUMMARY_DTYPE scalar, whose next_bucket and
+        next_hash are the cursor to go on with);
+        segments.enumerate_objects splits the payload.  On a spoiled table
+        the payload is empty and summary["spoiled"] is 1."""
+        from . import segments as _seg
+        if stale is None:
+            stale = []
+        if not (isinstance(stale, np.ndarray) and stale.dtype == _seg.ENUM_FRAME_DTYPE):
+            stale = _seg.enum_frames(stale)
+        stale = np.ascontiguousarray(stale)
+        # no payload is longer than every held object sent once, 4 bytes and
+        # at most the log entry each
+        held = sum(int(k[2][:, 2].sum()) + 4 * k[2].shape[0] for k in self._keep if k is not None)
+        if payload_capacity is None:
+            payload_capacity = min(int(max_bytes), held)
+        room = min(int(payload_capacity), held)
+        payload = np.zeros(room, np.uint8)
+        summary = np.zeros(1, _seg.ENUMERATE_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_enumerate_host(
+            self._h, int(table_id), int(first_hash), int(last_hash), int(bucket_index),
+            int(bucket_next_hash), int(bucket_limit), p(stale), stale.shape[0],
+            _seg.ENUM_KEYS_ONLY if keys_only else 0, p(payload), room, int(max_bytes), p(summary))
+        _check(rc, "ramcrc_replay_table_enumerate_host")
+        return payload[:int(summary[0]["payload_bytes"])], summary[0]
 
     def write(self, data, reqs, out_capacity, next_version, timestamp=0, rules=None,
               key_hash=None, batch_segment_id=None, want_refs=True, want_old=False):
@@ -1311,6 +1351,45 @@ class ReplayTable:
             _ptr(parts), _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_read_hashes_device")
         return reply
+
+    def enumerate(self, table_id, payload, summary, max_bytes, first_hash=0,
+                  last_hash=0xFFFFFFFFFFFFFFFF, bucket_index=0, bucket_next_hash=0, bucket_limit=0,
+                  stale=None, keys_only=False, payload_capacity=None, stream=None):
+        """One reply of a table enumeration, packed on the device
+        (ramcrc_replay_table_enumerate_device): the objects of table_id with
+        first_hash <= hash <= last_hash, bucket by bucket from the cursor
+        (bucket_index, bucket_next_hash) up to bucket_limit (0: every bucket),
+        as {u32 length, log entry} entries that end within max_bytes.
+        payload: uint8 CUDA out, any alignment (payload_capacity: its size in
+        bytes, default payload.numel()); summary: int64 CUDA [11] out
+        (segments.ENUMERATE_SUMMARY_DTYPE), whose next_bucket and next_hash are
+        the cursor to go on with; stale: the iterator's stale frames, host
+        memory (segments.enum_frames or its rows), read before the call
+        returns; keys_only: entries end before the value.  The payload must
+        not overlap an added batch.  Read-only on the table.  Asynchronous;
+        segments.enumerate_objects splits the payload on the host."""
+        from . import segments as _seg
+        if stale is None:
+            stale = []
+        if not (isinstance(stale, np.ndarray) and stale.dtype == _seg.ENUM_FRAME_DTYPE):
+            stale = _seg.enum_frames(stale)
+        stale = np.ascontiguousarray(stale)
+        if payload_capacity is None:
+            payload_capacity = 0 if payload is None else payload.numel() * payload.element_size()
+        nbytes = lambda x: x.numel() * x.element_size()
+        if payload_capacity and (payload is None or nbytes(payload) < payload_capacity):
+            raise RamcrcError("ReplayTable.enumerate: payload is smaller than payload_capacity")
+        if summary is None or nbytes(summary) < 88:
+            raise RamcrcError("ReplayTable.enumerate: summary is smaller than 88 bytes")
+        rc = lib().ramcrc_replay_table_enumerate_device(
+            self._h, int(table_id), int(first_hash), int(last_hash), int(bucket_index),
+            int(bucket_next_hash), int(bucket_limit),
+            _c.c_void_p(stale.ctypes.data) if stale.shape[0] else None, stale.shape[0],
+            _seg.ENUM_KEYS_ONLY if keys_only else 0,
+            _ptr(payload) if payload_capacity else None, int(payload_capacity), int(max_bytes),
+            _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_enumerate_device")
+        return payload
 
     def write(self, data, reqs, out, out_cert, parts, summary, next_version, timestamp=0,
               rules=None, key_hash=None, batch_segment_id=None, refs=None, old=None,

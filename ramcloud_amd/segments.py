@@ -85,6 +85,15 @@ READ_HASHES_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "hashes", "objects", "objects_counted", "reply_bytes", "value_bytes", "key_bytes", "empty",
     "tombstones", "spoiled")])
 READ_HASHES_OBJECT_DTYPE = np.dtype([("version", "<u8"), ("length", "<u4")])   # packed
+# ramcrc_enum_frame (EnumerationIterator::Frame) and ramcrc_enumerate_summary
+# (ramcrc_replay_table_enumerate_device / _host)
+ENUM_FRAME_DTYPE = np.dtype([(n, "<u8") for n in (
+    "tablet_start_hash", "tablet_end_hash", "num_buckets", "bucket_index", "bucket_next_hash")])
+ENUMERATE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "num_buckets", "next_bucket", "next_hash", "objects", "payload_bytes", "value_bytes", "key_bytes",
+    "tombstones", "full", "stuck", "spoiled")])
+ENUM_KEYS_ONLY = 1
+ENUM_MAX_STALE = 8
 # ramcrc_write_req, ramcrc_write_ref, ramcrc_write_summary, the packed
 # MultiOp::Response::WritePart and ramcrc_seg_cert
 # (ramcrc_replay_table_write_device / _host)
@@ -278,6 +287,45 @@ def read_hashes_objects(reply, objects):
         out.append((version, raw[at:at + length]))
         at += length
     return out
+
+
+def enumerate_objects(payload, payload_bytes):
+    """The entries of an enumeration's payload (bytes or a uint8 array), of
+    which payload_bytes are valid, as a list of bytes: a u32 little-endian
+    length each, followed by that many bytes of the object's log entry."""
+    raw = np.ascontiguousarray(payload, np.uint8).reshape(-1).tobytes() \
+        if not isinstance(payload, (bytes, bytearray)) else bytes(payload)
+    end = int(payload_bytes)
+    if end > len(raw):
+        raise ValueError("enumerate_objects: payload_bytes is past the payload")
+    out, at = [], 0
+    while at < end:
+        if at + 4 > end:
+            raise ValueError("enumerate_objects: the payload ends inside a length")
+        length = int.from_bytes(raw[at:at + 4], "little")
+        at += 4
+        if at + length > end:
+            raise ValueError("enumerate_objects: the payload ends inside an object")
+        out.append(raw[at:at + length])
+        at += length
+    return out
+
+
+def enum_frames(frames):
+    """ENUM_FRAME_DTYPE array from (tablet_start_hash, tablet_end_hash,
+    num_buckets, bucket_index, bucket_next_hash) rows: the stale frames of an
+    enumeration, at most ENUM_MAX_STALE of them, each num_buckets a power of
+    two."""
+    frames = list(frames)
+    if len(frames) > ENUM_MAX_STALE:
+        raise ValueError("enum_frames: more than ENUM_MAX_STALE frames")
+    a = np.zeros(len(frames), ENUM_FRAME_DTYPE)
+    for i, row in enumerate(frames):
+        a[i] = tuple(int(v) for v in row)
+        nb = int(a[i]["num_buckets"])
+        if nb == 0 or nb & (nb - 1):
+            raise ValueError("enum_frames: num_buckets must be a power of two")
+    return a
 
 
 def tablets_array(rows):
