@@ -337,9 +337,9 @@ class Crc32CBatch {
 class ReplayTable {
   public:
     ReplayTable(Crc32CBatch& batch, uint64_t keyCap, uint32_t maxBatches)
-        : table(NULL)
+        : table(NULL), ctx(batch.context())
     {
-        check(ramcrc_replay_table_create(batch.context(), keyCap, maxBatches, &table),
+        check(ramcrc_replay_table_create(ctx, keyCap, maxBatches, &table),
               "ramcrc_replay_table_create");
     }
 
@@ -478,6 +478,50 @@ class ReplayTable {
               "ramcrc_replay_table_enumerate_device");
     }
 
+    /// An indexlet's entries from the table, sorted on the device: for every
+    /// object of tableId that the table holds now, its key indexId (>= 1, non
+    /// empty: the keys MasterService::requestInsertIndexEntries sends,
+    /// src/MasterService.cc:1993-2032) with the hash of its primary key, in
+    /// the B-tree's order (key, then hash).  d_entries and d_hashes hold
+    /// entryCapacity entries, d_indexKeys the index's own copy of its keys;
+    /// with all three NULL and both capacities 0 the call only sizes
+    /// (d_summary->entries_needed, key_bytes_needed).  The index is rebuilt,
+    /// not edited, and stays usable, merely stale, across later adds and
+    /// cleans.  Read-only on the table.
+    void
+    buildIndex(uint64_t tableId, uint8_t indexId, ramcrc_index_entry* d_entries,
+               uint64_t entryCapacity, uint64_t* d_hashes, void* d_indexKeys, uint64_t keysCapacity,
+               ramcrc_index_build_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_index_build_device(table, tableId, indexId, d_entries, entryCapacity,
+                                                     d_hashes, d_indexKeys, keysCapacity, d_summary,
+                                                     stream),
+              "ramcrc_replay_table_index_build_device");
+    }
+
+    /// A batch of IndexletManager::lookupIndexKeys
+    /// (src/IndexletManager.cc:611-709) over the arrays buildIndex wrote, on
+    /// the table's context: per query the hashes of the entries from {first
+    /// key, firstAllowedKeyHash} through the last key, at most max_hashes of
+    /// them, packed back to back in d_outHashes -- what readHashes takes --,
+    /// and the next key and hash to go on with (nextKeyLength, nextKeyHash)
+    /// when there are more.  Which indexlet owns a key, and
+    /// STATUS_UNKNOWN_INDEXLET, stay with the caller.  Stream-ordered after the
+    /// build: the number of entries is read from d_buildSummary on the device.
+    void
+    lookupIndexKeys(const ramcrc_index_entry* d_entries, const uint64_t* d_hashes,
+                    const void* d_indexKeys, const ramcrc_index_build_summary* d_buildSummary,
+                    const void* d_qkeys, uint64_t qkeysBytes, const ramcrc_index_query* d_queries,
+                    uint64_t nQueries, uint64_t* d_outHashes, uint64_t outCapacity,
+                    ramcrc_index_result* d_results, ramcrc_index_lookup_summary* d_summary,
+                    void* stream = NULL)
+    {
+        check(ramcrc_index_lookup_device(ctx, d_entries, d_hashes, d_indexKeys, d_buildSummary, d_qkeys,
+                                         qkeysBytes, d_queries, nQueries, d_outHashes, outCapacity,
+                                         d_results, d_summary, stream),
+              "ramcrc_index_lookup_device");
+    }
+
     /// MasterService::multiWrite (src/MasterService.cc:1523-1601) for nReqs
     /// keysAndValue images, on the device: per request the lookup above, the
     /// RejectRules, the new version as ObjectManager::writeObject chooses it
@@ -610,6 +654,7 @@ class ReplayTable {
     }
 
     ramcrc_replay_table* table;
+    ramcrc_ctx* ctx;   // the batch's: an index lookup takes a context, not a table
 
     ReplayTable(const ReplayTable&);             // not copyable
     ReplayTable& operator=(const ReplayTable&);

@@ -1150,6 +1150,196 @@ int ramcrc_replay_table_enumerate_host(ramcrc_replay_table_host* t, uint64_t tab
         void* payload, uint64_t payload_capacity, uint64_t max_bytes,
         ramcrc_enumerate_summary* summary);
 
+/* A secondary index over the table, built and searched on the device: the
+ * indexlet's half of an indexed read (IndexLookup: LOOKUP_INDEX_KEYS, then
+ * READ_HASHES).  index_build extracts the {secondary key, primary-key hash}
+ * entries of one table id and key index from the table's winners and sorts
+ * them (IndexletManager::insertEntry, src/IndexletManager.cc:578-604, for
+ * every key MasterService::requestInsertIndexEntries would send,
+ * src/MasterService.cc:1993-2032); index_lookup is a batch of
+ * IndexletManager::lookupIndexKeys (:611-709) over the sorted entries.  Its
+ * hashes go to ramcrc_replay_table_read_hashes_device unchanged, on the same
+ * stream, without a host round trip.  Rules marked "ours" cover what the
+ * reference leaves open or where this form differs.
+ *
+ * Selection.  A claimed slot is selected when its key's winner now is an
+ * OBJECT, its claimant's table id equals table_id -- ours: all 64 bits --, the
+ * winner has more than index_id keys, its key table and keys lie within its
+ * payload (the lookup's rule for a broken key table: such an object gets no
+ * entry), a cumulative key length that shrinks or passes the last one gives no
+ * entry either, and key index_id has length > 0.  Tombstone winners and
+ * absent keys give no entry.  objects_seen counts the slots selected by table
+ * id with an object winner, indexed or not.
+ *
+ * Entry.  {prefix, pk_hash, key_off, key_len, reserved = 0}, 32 bytes.  prefix
+ * is the key's first 8 bytes as a big-endian integer, zero-padded on the
+ * right.  pk_hash is the slot's record hash exactly as the read-hashes call
+ * defines it (the hash the claimant's batch was added with, Key::getHash of
+ * the claimant's key otherwise).  The key's bytes are copied to d_index_keys +
+ * key_off: the index owns its keys and nothing in it points into an added
+ * batch, so it stays valid, and merely stale, after later adds and after a
+ * clean has handed the victims' segments back.  A stale entry is harmless as
+ * in the reference: read_hashes and the client's isKeyInRange filter it.
+ *
+ * Order.  Ascending by key, then by pk_hash (key_less,
+ * src/btreeRamCloud/Btree.h:1978-1985).  Keys compare as IndexKey::keyCompare
+ * (src/IndexKey.cc:41-59) compares non-empty keys: memcmp over the common
+ * length, bytes unsigned, then the shorter key first.  d_hashes[i] ==
+ * d_entries[i].pk_hash for every i < n_entries, so a lookup's reply is a
+ * contiguous copy.  Ours: entries equal in key and hash (two primary keys of
+ * one 64-bit hash with the same secondary key; the tree would hold one) are
+ * all kept, in unspecified relative order.  Ours: where a key lies in
+ * d_index_keys is unspecified (slot order may show there and nowhere else);
+ * the keys take key_bytes bytes from d_index_keys + 0, back to back.
+ *
+ * Summary and capacity.  entries_needed and key_bytes_needed are what the
+ * selection comes to.  When entries_needed > entry_capacity or
+ * key_bytes_needed > keys_capacity: overflow = 1, n_entries = key_bytes = 0
+ * and no byte of d_entries, d_hashes and d_index_keys is written.  The call
+ * with all three NULL and both capacities 0 is the sizing call.  Otherwise
+ * n_entries = entries_needed, key_bytes = key_bytes_needed, and nothing at or
+ * past them is written.  On a spoiled table the arrays stay untouched and the
+ * summary is all zero with spoiled = 1.  The call changes no table word,
+ * descriptor, work array or batch counter.
+ *
+ * RAMCRC_EINVAL before any launch: t or d_summary NULL; index_id == 0 (the
+ * primary key is no index; an index_id above 255 selects nothing); d_entries or d_hashes NULL with
+ * entry_capacity > 0; d_index_keys NULL with keys_capacity > 0;
+ * entry_capacity >= 2^32 - 1; d_entries not 16-byte aligned, d_hashes or
+ * d_summary not 8-byte aligned.  The outputs must not overlap any added
+ * batch or each other; the call cannot check this.
+ *
+ * Scratch comes from the context: 32 + 16 * ceil(S / 256) words for the S
+ * slots of the table, and, when entry_capacity exceeds one sort tile of 1,024
+ * entries, 4 * entry_capacity entries for the merge passes' second buffer.
+ * After ramcrc_ctx_reserve(ctx, 32 + 16 * ceil(S / 256), 4 * entry_capacity) a
+ * build does not allocate.  The number of launches follows entry_capacity,
+ * never the table's contents: the call is stream-ordered, asynchronous and
+ * capturable and makes no host sync; lifetime and concurrency are the table's.
+ *
+ * Not done: insertEntry and removeEntry one at a time -- an index is rebuilt,
+ * not edited --; the indexlet's boundaries (findIndexlet, firstNotOwnedKey,
+ * STATUS_UNKNOWN_INDEXLET), the RPC header and the transport, which stay with
+ * the master. */
+typedef struct ramcrc_index_entry {      /* 32 bytes */
+    uint64_t prefix;                     /* the key's first 8 bytes, big-endian, zero-padded */
+    uint64_t pk_hash;                    /* the primary key's record hash */
+    uint64_t key_off;                    /* the key's bytes: d_index_keys + key_off */
+    uint32_t key_len;                    /* 1 .. 65,535 */
+    uint32_t reserved;                   /* written as 0 */
+} ramcrc_index_entry;
+
+typedef struct ramcrc_index_build_summary {
+    uint64_t n_entries, key_bytes;       /* what was written; 0 on overflow */
+    uint64_t entries_needed, key_bytes_needed;
+    uint64_t objects_seen;               /* object winners of table_id, indexed or not */
+    uint64_t overflow;
+    uint64_t spoiled;
+} ramcrc_index_build_summary;
+
+int ramcrc_replay_table_index_build_device(ramcrc_replay_table* t, uint64_t table_id, uint32_t index_id,
+                                           ramcrc_index_entry* d_entries, uint64_t entry_capacity,
+                                           uint64_t* d_hashes, void* d_index_keys, uint64_t keys_capacity,
+                                           ramcrc_index_build_summary* d_summary, void* stream);
+
+/* The same on the host table, single-threaded: host pointers, no alignment
+ * rules, the same entries (std::stable_sort under the same comparator).  The
+ * keys lie in d_index_keys in slot order of the host table, which may differ
+ * from the device's: compare entries with key_off dereferenced. */
+int ramcrc_replay_table_index_build_host(ramcrc_replay_table_host* t, uint64_t table_id, uint32_t index_id,
+                                         ramcrc_index_entry* entries, uint64_t entry_capacity,
+                                         uint64_t* hashes, void* index_keys, uint64_t keys_capacity,
+                                         ramcrc_index_build_summary* summary);
+
+/* A batch of IndexletManager::lookupIndexKeys (src/IndexletManager.cc:654-706)
+ * over a built index.  The call takes a context, not a table: an index is
+ * self-contained.  n_entries is read from d_build_summary on the device, so a
+ * build and a lookup chain on one stream without a sync.
+ *
+ * Query.  {first_off, last_off, first_allowed_hash, first_len, last_len,
+ * max_hashes, reserved = 0}, 40 bytes; the two keys lie at d_qkeys + first_off
+ * and + last_off.  lo is the first entry not less than {first key,
+ * first_allowed_hash} in the build's order (:654-662); hi is the first entry
+ * whose key compares greater than the last key (:667).  The query returns num
+ * = min(hi - lo, max_hashes) hashes, d_hashes[lo .. lo + num).  When hi - lo >
+ * max_hashes it also returns the next entry to fetch (:686-690): next_entry =
+ * lo + num, next_key_hash that entry's pk_hash, next_key_off and next_key_len
+ * its key in d_index_keys; otherwise the four are 0.  An empty last key is
+ * unbounded above, as keyCompare's keyLength2 == 0 rule makes it at :667.
+ * Ours: an empty first key is below every entry.  The reference's comparator
+ * is no consistent order for an empty first key -- keyCompare(x, empty) == -1
+ * and keyCompare(empty, x) < 0 both hold --, and what its tree then returns is
+ * an accident of the tree's shape.  A first key above the last key returns
+ * nothing.  A query whose key ranges run past qkeys_bytes, a length > 65,535
+ * or reserved != 0 is RAMCRC_INDEX_BAD_QUERY with no hashes; nothing is read
+ * for it, as for the lookup's bad keys.
+ *
+ * Reply.  Queries are served in order and their hashes packed back to back in
+ * d_out_hashes; out_off counts hashes.  The first query whose hashes would
+ * end past out_capacity, and every later one, is RAMCRC_INDEX_NOT_SERVED and
+ * writes no hash.  A result that is BAD_QUERY or NOT_SERVED is {out_off =
+ * RAMCRC_READ_NONE, status, every other field 0}.  Summary: served counts the
+ * leading queries that were not NOT_SERVED, bad ones included; hashes what was
+ * written; bad and maxed_out (hi - lo > max_hashes) cover the served ones;
+ * n_entries is the index's.  overflow_index = 1 when the build summary says
+ * overflow or spoiled: then every query is NOT_SERVED and the other fields
+ * are 0.  No word of d_out_hashes at or past `hashes` is written.
+ *
+ * RAMCRC_EINVAL before any launch: ctx, d_build_summary or d_summary NULL;
+ * n_queries >= 2^32 - 1; d_queries or d_results NULL with n_queries > 0;
+ * d_qkeys NULL with qkeys_bytes > 0; d_out_hashes NULL with out_capacity > 0;
+ * a structure or hash array not 8-byte aligned (d_entries: 16).  d_entries,
+ * d_hashes and d_index_keys may be NULL only for an index of no entries.  The
+ * three arrays must be a build's: the call trusts key_off and key_len.
+ *
+ * Scratch comes from the context: 32 + 16 * ceil(n_queries / 256) words and 2 *
+ * n_queries entries; after ramcrc_ctx_reserve(ctx, 32 + 16 * ceil(n / 256), 2 *
+ * n) a call of up to n queries does not allocate.  Stream-ordered,
+ * asynchronous, capturable, no host sync. */
+#define RAMCRC_INDEX_OK         0u
+#define RAMCRC_INDEX_BAD_QUERY  1u
+#define RAMCRC_INDEX_NOT_SERVED 2u
+
+typedef struct ramcrc_index_query {      /* 40 bytes */
+    uint64_t first_off, last_off;        /* the keys' places in d_qkeys */
+    uint64_t first_allowed_hash;
+    uint32_t first_len, last_len;        /* 0: unbounded below / above */
+    uint32_t max_hashes;
+    uint32_t reserved;                   /* must be 0 */
+} ramcrc_index_query;
+
+typedef struct ramcrc_index_result {     /* 48 bytes */
+    uint64_t out_off;                    /* in hashes; RAMCRC_READ_NONE: no answer */
+    uint64_t next_entry;
+    uint64_t next_key_hash;
+    uint64_t next_key_off;
+    uint32_t num_hashes;
+    uint32_t next_key_len;               /* 0: the range is exhausted */
+    uint32_t status;
+    uint32_t reserved;                   /* written as 0 */
+} ramcrc_index_result;
+
+typedef struct ramcrc_index_lookup_summary {
+    uint64_t served, hashes, bad, maxed_out;
+    uint64_t n_entries;
+    uint64_t overflow_index;
+} ramcrc_index_lookup_summary;
+
+int ramcrc_index_lookup_device(ramcrc_ctx* ctx, const ramcrc_index_entry* d_entries, const uint64_t* d_hashes,
+                               const void* d_index_keys, const ramcrc_index_build_summary* d_build_summary,
+                               const void* d_qkeys, uint64_t qkeys_bytes, const ramcrc_index_query* d_queries,
+                               uint64_t n_queries, uint64_t* d_out_hashes, uint64_t out_capacity,
+                               ramcrc_index_result* d_results, ramcrc_index_lookup_summary* d_summary,
+                               void* stream);
+
+/* The same on the host, single-threaded: host pointers, no alignment rules,
+ * the same bytes. */
+int ramcrc_index_lookup_host(const ramcrc_index_entry* entries, const uint64_t* hashes, const void* index_keys,
+                             const ramcrc_index_build_summary* build_summary, const void* qkeys,
+                             uint64_t qkeys_bytes, const ramcrc_index_query* queries, uint64_t n_queries,
+                             uint64_t* out_hashes, uint64_t out_capacity, ramcrc_index_result* results,
+                             ramcrc_index_lookup_summary* summary);
+
 /* A multi-write: the loop of MasterService::multiWrite
  * (src/MasterService.cc:1523-1601) over ObjectManager::writeObject
  * (src/ObjectManager.cc:1181-1350), against the replay table.  The call does

@@ -65,6 +65,7 @@
 //                         its lookup by key and a multi-read's reply)
 //   dev_read_hashes.inc   k_rh_* (an indexed read's reply: objects by primary-key hash)
 //   dev_enumerate.inc     k_en_* (one reply of a table enumeration: a walk over the buckets)
+//   dev_index.inc         k_ix_*, k_ixl_* (a secondary index: sorted entries and range lookups)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -87,6 +88,7 @@
 #include "read_rules.h"
 #include "read_hashes_rules.h"
 #include "enumerate_rules.h"
+#include "index_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -118,6 +120,7 @@ using ramcrc::OpTable;
 #include "dev_replay_table.inc"
 #include "dev_read_hashes.inc"
 #include "dev_enumerate.inc"
+#include "dev_index.inc"
 #include "dev_write.inc"
 #include "dev_remove.inc"
 #include "dev_increment.inc"
@@ -1694,6 +1697,137 @@ int ramcrc_replay_table_enumerate_device(ramcrc_replay_table* t, uint64_t table_
     HIPCHK(hipGetLastError());
     if (nb) {
         hipLaunchKernelGGL(k_en_gather, grid, dim3(kPartThreads), 0, s, a, r);
+        HIPCHK(hipGetLastError());
+    }
+    return RAMCRC_OK;
+}
+
+int ramcrc_replay_table_index_build_device(ramcrc_replay_table* t, uint64_t table_id, uint32_t index_id,
+                                           ramcrc_index_entry* d_entries, uint64_t entry_capacity,
+                                           uint64_t* d_hashes, void* d_index_keys, uint64_t keys_capacity,
+                                           ramcrc_index_build_summary* d_summary, void* stream)
+{
+    if (!t || !d_summary || index_id == 0 || entry_capacity >= 0xFFFFFFFFull ||
+        (entry_capacity && (!d_entries || !d_hashes)) || (keys_capacity && !d_index_keys))
+        return RAMCRC_EINVAL;
+    const uint64_t K = reinterpret_cast<uint64_t>(d_index_keys);
+    if ((reinterpret_cast<uint64_t>(d_entries) & 15) || (reinterpret_cast<uint64_t>(d_hashes) & 7) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || K > UINT64_MAX - keys_capacity)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: a line for the scan's words to the later launches, then the
+    // tile sums of the slots, in the chunk-partial buffer; the merge passes'
+    // second buffer in the plan buffer, when there is a merge pass (ramcrc.h
+    // states these sizes)
+    const uint64_t ntiles = (t->nslots + kPartThreads - 1) / kPartThreads;
+    uint32_t passes = 0;
+    for (uint64_t W = kIxTile; W < entry_capacity; W *= 2)
+        passes++;
+    int rc = reserve_locked(c, kLookCountWords + 2 * kIxTileStride * ntiles, passes ? 4 * entry_capacity : 0);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    IxDesc r{};
+    r.table_id = table_id;
+    r.index_id = index_id;
+    r.entries = d_entries;
+    r.ecap = entry_capacity;
+    r.hashes = d_hashes;
+    r.keys = K;
+    r.kcap = keys_capacity;
+    r.summary = d_summary;
+    r.head = reinterpret_cast<unsigned long long*>(c->partials);
+    r.tile = reinterpret_cast<uint64_t*>(c->partials + kLookCountWords);
+    HIPCHK(hipMemsetAsync(c->partials, 0,
+                          kLookCountWords * sizeof(uint32_t) + kIxTileStride * ntiles * sizeof(uint64_t), s));
+    const dim3 grid(rtab_grid(c, t->nslots, kPartThreads));
+    hipLaunchKernelGGL(k_ix_size, grid, dim3(kPartThreads), 0, s, a, r);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(kPartThreads), 0, s, a, r);
+    HIPCHK(hipGetLastError());
+    if (entry_capacity == 0)
+        return RAMCRC_OK;
+    hipLaunchKernelGGL(k_ix_emit, grid, dim3(kPartThreads), 0, s, a, r);
+    HIPCHK(hipGetLastError());
+    // the tile sort leaves its output where an even number of passes ends in d_entries
+    ramcrc_index_entry* const other = reinterpret_cast<ramcrc_index_entry*>(c->plan_local);
+    ramcrc_index_entry* src = (passes & 1) ? other : d_entries;
+    const dim3 sgrid(rtab_grid(c, entry_capacity, kIxTile));
+    hipLaunchKernelGGL(k_ix_sort, sgrid, dim3(kPartThreads), 0, s, a, r, src);
+    HIPCHK(hipGetLastError());
+    for (uint64_t W = kIxTile; W < entry_capacity; W *= 2) {
+        ramcrc_index_entry* const dst = src == other ? d_entries : other;
+        hipLaunchKernelGGL(k_ix_merge, sgrid, dim3(kPartThreads), 0, s, a, r, W, src, dst);
+        HIPCHK(hipGetLastError());
+        src = dst;
+    }
+    hipLaunchKernelGGL(k_ix_hashes, dim3(rtab_grid(c, entry_capacity, kPartThreads)), dim3(kPartThreads), 0, s,
+                       a, r);
+    HIPCHK(hipGetLastError());
+    return RAMCRC_OK;
+}
+
+int ramcrc_index_lookup_device(ramcrc_ctx* c, const ramcrc_index_entry* d_entries, const uint64_t* d_hashes,
+                               const void* d_index_keys, const ramcrc_index_build_summary* d_build_summary,
+                               const void* d_qkeys, uint64_t qkeys_bytes, const ramcrc_index_query* d_queries,
+                               uint64_t n_queries, uint64_t* d_out_hashes, uint64_t out_capacity,
+                               ramcrc_index_result* d_results, ramcrc_index_lookup_summary* d_summary,
+                               void* stream)
+{
+    if (!c || !d_build_summary || !d_summary || n_queries >= 0xFFFFFFFFull ||
+        (n_queries && (!d_queries || !d_results)) || (qkeys_bytes && !d_qkeys) ||
+        (out_capacity && !d_out_hashes))
+        return RAMCRC_EINVAL;
+    const uint64_t Q = reinterpret_cast<uint64_t>(d_qkeys);
+    if ((reinterpret_cast<uint64_t>(d_entries) & 15) || (reinterpret_cast<uint64_t>(d_hashes) & 7) ||
+        (reinterpret_cast<uint64_t>(d_build_summary) & 7) || (reinterpret_cast<uint64_t>(d_queries) & 7) ||
+        (reinterpret_cast<uint64_t>(d_out_hashes) & 7) || (reinterpret_cast<uint64_t>(d_results) & 7) ||
+        (reinterpret_cast<uint64_t>(d_summary) & 7) || Q > UINT64_MAX - qkeys_bytes)
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch: a line for the scan's word to the copy, then the tile sums, in
+    // the chunk-partial buffer; two words a query in the plan buffer
+    // (ramcrc.h states these sizes)
+    const uint64_t ntiles = (n_queries + kPartThreads - 1) / kPartThreads;
+    int rc = reserve_locked(c, kLookCountWords + 2 * kIxTileStride * ntiles, 2 * n_queries);
+    if (rc)
+        return rc;
+    IxlDesc r{};
+    r.entries = d_entries;
+    r.hashes = d_hashes;
+    r.keys = reinterpret_cast<uint64_t>(d_index_keys);
+    r.build = d_build_summary;
+    r.qkeys = Q;
+    r.qkeys_bytes = qkeys_bytes;
+    r.queries = reinterpret_cast<const uint64_t*>(d_queries);
+    r.nq = n_queries;
+    r.out = d_out_hashes;
+    r.ocap = out_capacity;
+    r.results = d_results;
+    r.summary = d_summary;
+    r.rec = c->plan_local;
+    r.head = reinterpret_cast<unsigned long long*>(c->partials);
+    r.tile = reinterpret_cast<uint64_t*>(c->partials + kLookCountWords);
+    const dim3 grid(rtab_grid(c, n_queries, kPartThreads));
+    HIPCHK(hipMemsetAsync(c->partials, 0,
+                          kLookCountWords * sizeof(uint32_t) + kIxTileStride * ntiles * sizeof(uint64_t), s));
+    if (n_queries) {
+        hipLaunchKernelGGL(k_ixl_search, grid, dim3(kPartThreads), 0, s, r);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ixl_scan, dim3(1), dim3(kPartThreads), 0, s, r);
+    HIPCHK(hipGetLastError());
+    if (n_queries) {
+        hipLaunchKernelGGL(k_ixl_copy, grid, dim3(kPartThreads), 0, s, r);
+        HIPCHK(hipGetLastError());
+        // (the wide ranges: a grid for the output, not for the queries)
+        hipLaunchKernelGGL(k_ixl_long, dim3(rtab_grid(c, out_capacity, kPartThreads)), dim3(kPartThreads), 0, s, r);
         HIPCHK(hipGetLastError());
     }
     return RAMCRC_OK;

@@ -31,6 +31,7 @@
 #include "read_rules.h"
 #include "read_hashes_rules.h"
 #include "enumerate_rules.h"
+#include "index_rules.h"
 #include "resolve_rules.h"
 #include "sidelog_rules.h"
 #include "write_rules.h"
@@ -1293,6 +1294,177 @@ int ramcrc_replay_table_enumerate_host(ramcrc_replay_table_host* t, uint64_t tab
     sm.value_bytes = all.value_bytes;
     sm.key_bytes = all.key_bytes;
     memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+    return RAMCRC_OK;
+}
+
+// A secondary index (the rules of index_rules.h): slot by slot the object
+// winners of the table id, the key of the asked index, its copy; then
+// std::stable_sort under the shared comparator.
+extern "C++" {
+namespace {
+struct IxBytes {
+    const uint8_t* p;
+    uint32_t operator[](uint32_t i) const { return p[i]; }
+};
+
+ramcrc_ix::KeyRef<IxBytes> ix_ref(const ramcrc_index_entry& e, const uint8_t* keys)
+{
+    return ramcrc_ix::KeyRef<IxBytes>{e.prefix, e.key_len, IxBytes{keys + e.key_off + ramcrc_ix::kPrefixBytes}};
+}
+
+ramcrc_ix::KeyRef<IxBytes> ix_query_ref(const uint8_t* key, uint32_t len)
+{
+    return ramcrc_ix::KeyRef<IxBytes>{ramcrc_ix::prefix_of(IxBytes{key}, len), len,
+                                      IxBytes{key + ramcrc_ix::kPrefixBytes}};
+}
+}  // namespace
+}
+
+int ramcrc_replay_table_index_build_host(ramcrc_replay_table_host* t, uint64_t table_id, uint32_t index_id,
+                                         ramcrc_index_entry* entries, uint64_t entry_capacity,
+                                         uint64_t* hashes, void* index_keys, uint64_t keys_capacity,
+                                         ramcrc_index_build_summary* summary)
+{
+    namespace ix = ramcrc_ix;
+    if (!t || !summary || index_id == 0 || entry_capacity >= 0xFFFFFFFFull ||
+        (entry_capacity && (!entries || !hashes)) || (keys_capacity && !index_keys))
+        return RAMCRC_EINVAL;
+    ramcrc_index_build_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+        return RAMCRC_OK;
+    }
+    struct Found {
+        const uint8_t* key;
+        uint32_t len;
+        uint64_t hash;
+    };
+    try {
+        std::vector<Found> found;
+        for (const ramcrc_replay_table_host::Slot& sl : t->slots) {
+            if (!sl.claim || sl.table_id != table_id || !((sl.rank >> 48) & 1))
+                continue;
+            sm.objects_seen++;
+            const uint32_t wb = uint32_t(sl.rank >> 32) & 0xFFFFu, wr = uint32_t(sl.rank);
+            const ramcrc_replay_table_host::Batch& bt = t->batches[wb];
+            ramcrc_seg_entry r;   // (a survivor's table has no alignment rule)
+            memcpy(&r, reinterpret_cast<const uint8_t*>(bt.entries) + uint64_t(wr) * sizeof(r), sizeof(r));
+            const uint32_t po = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+            const LookRd rd{bt.base + r.segment * bt.stride + po};
+            const ix::KeyAt k = ix::key_at(r.length, rd, index_id);
+            if (k.len == 0)
+                continue;
+            const ramcrc_replay_table_host::Batch& cb = t->batches[sl.claim >> 32];
+            uint64_t h;   // the claimant's record hash
+            if (cb.key_hash)
+                memcpy(&h, reinterpret_cast<const uint8_t*>(cb.key_hash) + ((sl.claim & 0xFFFFFFFFull) - 1) * 8,
+                       8);
+            else
+                h = ramcrc::key_hash(sl.table_id, sl.key, sl.key_len);
+            found.push_back(Found{rd.pay + k.off, k.len, h});
+            sm.key_bytes_needed += k.len;
+        }
+        sm.entries_needed = found.size();
+        if (ix::overflow(sm.entries_needed, sm.key_bytes_needed, entry_capacity, keys_capacity)) {
+            sm.overflow = 1;
+            memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));
+            return RAMCRC_OK;
+        }
+        uint8_t* const kb = static_cast<uint8_t*>(index_keys);
+        std::vector<ramcrc_index_entry> es;
+        es.reserve(found.size());
+        uint64_t off = 0;
+        for (const Found& f : found) {
+            memcpy(kb + off, f.key, f.len);
+            es.push_back(ix::make_entry(ix::prefix_of(IxBytes{f.key}, f.len), f.hash, off, f.len));
+            off += f.len;
+        }
+        std::stable_sort(es.begin(), es.end(), [kb](const ramcrc_index_entry& x, const ramcrc_index_entry& y) {
+            return ix::entry_less(ix_ref(x, kb), x.pk_hash, ix_ref(y, kb), y.pk_hash);
+        });
+        for (size_t i = 0; i < es.size(); i++) {
+            memcpy(reinterpret_cast<uint8_t*>(entries) + i * sizeof(es[i]), &es[i], sizeof(es[i]));
+            memcpy(reinterpret_cast<uint8_t*>(hashes) + i * 8, &es[i].pk_hash, 8);
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    sm.n_entries = sm.entries_needed;
+    sm.key_bytes = sm.key_bytes_needed;
+    memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));
+    return RAMCRC_OK;
+}
+
+// A batch of lookupIndexKeys (the rules of index_rules.h): per query the two
+// binary searches; the loop stops serving at the first query whose hashes do
+// not fit.
+int ramcrc_index_lookup_host(const ramcrc_index_entry* entries, const uint64_t* hashes, const void* index_keys,
+                             const ramcrc_index_build_summary* build_summary, const void* qkeys,
+                             uint64_t qkeys_bytes, const ramcrc_index_query* queries, uint64_t n_queries,
+                             uint64_t* out_hashes, uint64_t out_capacity, ramcrc_index_result* results,
+                             ramcrc_index_lookup_summary* summary)
+{
+    namespace ix = ramcrc_ix;
+    if (!build_summary || !summary || n_queries >= 0xFFFFFFFFull || (n_queries && (!queries || !results)) ||
+        (qkeys_bytes && !qkeys) || (out_capacity && !out_hashes))
+        return RAMCRC_EINVAL;
+    ramcrc_index_build_summary bs;   // (no alignment rule)
+    memcpy(&bs, reinterpret_cast<const uint8_t*>(build_summary), sizeof(bs));
+    const bool dead = bs.overflow || bs.spoiled;
+    const uint64_t n = dead ? 0 : bs.n_entries;
+    const uint8_t* const kb = static_cast<const uint8_t*>(index_keys);
+    const uint8_t* const qb = static_cast<const uint8_t*>(qkeys);
+    const auto entry = [entries](uint64_t i) {
+        ramcrc_index_entry e;
+        memcpy(&e, reinterpret_cast<const uint8_t*>(entries) + i * sizeof(e), sizeof(e));
+        return e;
+    };
+    ramcrc_index_lookup_summary sm{};
+    sm.overflow_index = dead;
+    sm.n_entries = n;
+    bool open = !dead;   // every query so far was served
+    for (uint64_t i = 0; i < n_queries; i++) {
+        ramcrc_index_query q;
+        memcpy(&q, reinterpret_cast<const uint8_t*>(queries) + i * sizeof(q), sizeof(q));
+        ramcrc_index_result res = ix::no_result(RAMCRC_INDEX_NOT_SERVED);
+        if (open && ix::bad_query(q, qkeys_bytes)) {
+            res = ix::no_result(RAMCRC_INDEX_BAD_QUERY);
+            sm.served++;
+            sm.bad++;
+        } else if (open) {
+            const ix::KeyRef<IxBytes> first = ix_query_ref(qb + q.first_off, q.first_len);
+            const ix::KeyRef<IxBytes> last = ix_query_ref(qb + q.last_off, q.last_len);
+            const uint64_t lo = ix::first_false(n, [&](uint64_t m) {
+                const ramcrc_index_entry e = entry(m);
+                return ix::entry_less(ix_ref(e, kb), e.pk_hash, first, q.first_allowed_hash);
+            });
+            uint64_t hi = n;
+            if (q.last_len)
+                hi = ix::first_false(n, [&](uint64_t m) { return ix::key_compare(ix_ref(entry(m), kb), last) <= 0; });
+            const ix::Answer an = ix::answer(lo, hi, q.max_hashes);
+            if (ix::served(sm.hashes, an.num, out_capacity)) {
+                res = ramcrc_index_result{sm.hashes, 0ull, 0ull, 0ull, an.num, 0u, RAMCRC_INDEX_OK, 0u};
+                if (an.more) {
+                    const ramcrc_index_entry e = entry(lo + an.num);
+                    res.next_entry = lo + an.num;
+                    res.next_key_hash = e.pk_hash;
+                    res.next_key_off = e.key_off;
+                    res.next_key_len = e.key_len;
+                }
+                if (an.num)
+                    memcpy(reinterpret_cast<uint8_t*>(out_hashes) + sm.hashes * 8,
+                           reinterpret_cast<const uint8_t*>(hashes) + lo * 8, uint64_t(an.num) * 8);
+                sm.served++;
+                sm.hashes += an.num;
+                sm.maxed_out += an.more;
+            } else {
+                open = false;
+            }
+        }
+        memcpy(reinterpret_cast<uint8_t*>(results) + i * sizeof(res), &res, sizeof(res));
+    }
+    memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));
     return RAMCRC_OK;
 }
 

@@ -131,6 +131,10 @@ def lib():
                                                        u64, vp, vp]),
         "ramcrc_replay_table_enumerate_host": (i32, [vp, u64, u64, u64, u64, u64, u64, vp, u32, u32, vp, u64,
                                                      u64, vp]),
+        "ramcrc_replay_table_index_build_device": (i32, [vp, u64, u32, vp, u64, vp, vp, u64, vp, vp]),
+        "ramcrc_replay_table_index_build_host": (i32, [vp, u64, u32, vp, u64, vp, vp, u64, vp]),
+        "ramcrc_index_lookup_device": (i32, [vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp]),
+        "ramcrc_index_lookup_host": (i32, [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, vp]),
         "ramcrc_replay_table_write_device": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
                                                    vp, vp, vp, vp, vp, vp]),
         "ramcrc_replay_table_write_host": (i32, [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, u32,
@@ -433,6 +437,46 @@ def replay_resolve_host(segments, seg_stride, n_seg, status, entries, key_hash=N
     return winner, live[:min(need.value, cap)], need.value, counts[0]
 
 
+class Index:
+    """A built secondary index (ramcrc_replay_table_index_build_device / _host):
+    the sorted entries (segments.INDEX_ENTRY_DTYPE, 32 bytes each), the dense
+    copy of their hashes, the index's own copy of its keys and the build's
+    summary (segments.INDEX_BUILD_SUMMARY_DTYPE).  CUDA tensors for a device
+    index, numpy arrays for a host index.  An index is self-contained: it
+    outlives the table's later adds and cleans, merely going stale."""
+
+    def __init__(self, entries, hashes, index_keys, summary):
+        self.entries, self.hashes, self.index_keys, self.summary = entries, hashes, index_keys, summary
+
+
+def index_lookup_host(index, qkeys, queries, out_capacity=None):
+    """A batch of lookupIndexKeys over a host index (ramcrc_index_lookup_host).
+    qkeys: uint8 [qkeys_bytes]; queries: segments.INDEX_QUERY_DTYPE [n]
+    (segments.index_queries packs both); out_capacity: the reply's room in
+    hashes, default: room for every query's max_hashes, at most the index's
+    entries each.  Returns (out_hashes: uint64 [hashes], results:
+    segments.INDEX_RESULT_DTYPE [n], summary: a
+    segments.INDEX_LOOKUP_SUMMARY_DTYPE scalar);
+    segments.index_lookup_hashes splits the reply."""
+    from . import segments as _seg
+    qkeys = np.ascontiguousarray(qkeys, np.uint8).reshape(-1)
+    queries = np.ascontiguousarray(queries, _seg.INDEX_QUERY_DTYPE).reshape(-1)
+    n = queries.shape[0]
+    ne = int(index.summary["n_entries"])
+    if out_capacity is None:
+        out_capacity = int(np.minimum(queries["max_hashes"].astype(np.uint64), ne).sum())
+    out = np.zeros(int(out_capacity), np.uint64)
+    results = np.zeros(n, _seg.INDEX_RESULT_DTYPE)
+    summary = np.zeros(1, _seg.INDEX_LOOKUP_SUMMARY_DTYPE)
+    bs = np.array([index.summary], _seg.INDEX_BUILD_SUMMARY_DTYPE)
+    p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+    rc = lib().ramcrc_index_lookup_host(p(index.entries), p(index.hashes), p(index.index_keys), p(bs),
+                                        p(qkeys), qkeys.size, p(queries), n, p(out), out.size,
+                                        p(results), p(summary))
+    _check(rc, "ramcrc_index_lookup_host")
+    return out[:int(summary[0]["hashes"])], results, summary[0]
+
+
 class ReplayTableHost:
     """The persistent replay table on the host (ramcrc_replay_table_*_host):
     replay_resolve_host's decision fed batch by batch.  The table keeps the
@@ -645,6 +689,34 @@ class ReplayTableHost:
             _seg.ENUM_KEYS_ONLY if keys_only else 0, p(payload), room, int(max_bytes), p(summary))
         _check(rc, "ramcrc_replay_table_enumerate_host")
         return payload[:int(summary[0]["payload_bytes"])], summary[0]
+
+    def index_build(self, table_id, index_id, entry_capacity=None, keys_capacity=None):
+        """The sorted secondary index of table_id's key index_id (>= 1) over the
+        table's object winners (ramcrc_replay_table_index_build_host).
+        entry_capacity, keys_capacity: the arrays' room, default: what the
+        sizing call reports.  Returns an Index of numpy arrays, cut to what
+        was written, whose summary is a segments.INDEX_BUILD_SUMMARY_DTYPE
+        scalar; on overflow or a spoiled table the arrays are empty."""
+        from . import segments as _seg
+        summary = np.zeros(1, _seg.INDEX_BUILD_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        if entry_capacity is None or keys_capacity is None:
+            rc = lib().ramcrc_replay_table_index_build_host(self._h, int(table_id), int(index_id), None, 0,
+                                                            None, None, 0, p(summary))
+            _check(rc, "ramcrc_replay_table_index_build_host")
+            if entry_capacity is None:
+                entry_capacity = int(summary[0]["entries_needed"])
+            if keys_capacity is None:
+                keys_capacity = int(summary[0]["key_bytes_needed"])
+        entries = np.zeros(int(entry_capacity), _seg.INDEX_ENTRY_DTYPE)
+        hashes = np.zeros(int(entry_capacity), np.uint64)
+        keys = np.zeros(int(keys_capacity), np.uint8)
+        rc = lib().ramcrc_replay_table_index_build_host(
+            self._h, int(table_id), int(index_id), p(entries), entries.size, p(hashes), p(keys), keys.size,
+            p(summary))
+        _check(rc, "ramcrc_replay_table_index_build_host")
+        n, kb = int(summary[0]["n_entries"]), int(summary[0]["key_bytes"])
+        return Index(entries[:n], hashes[:n], keys[:kb], summary[0])
 
     def write(self, data, reqs, out_capacity, next_version, timestamp=0, rules=None,
               key_hash=None, batch_segment_id=None, want_refs=True, want_old=False):
@@ -974,6 +1046,42 @@ class Context:
 
     def reserve(self, max_chunks, max_entries):
         _check(lib().ramcrc_ctx_reserve(self._h, max_chunks, max_entries), "ramcrc_ctx_reserve")
+
+    def index_lookup(self, index, qkeys, queries, out_hashes, results, summary, qkeys_bytes=None,
+                     n_queries=None, out_capacity=None, stream=None):
+        """A batch of lookupIndexKeys over a built index, on the device
+        (ramcrc_index_lookup_device).  index: an Index of CUDA tensors, as
+        ReplayTable.index_build returns it; the number of entries is read from
+        its summary on the device, so a build and a lookup chain on one stream.
+        qkeys: uint8 CUDA, the queries' keys (qkeys_bytes default:
+        qkeys.numel()); queries: CUDA holding n segments.INDEX_QUERY_DTYPE
+        records (40 bytes each, 8-byte aligned; n_queries default: its bytes /
+        40); out_hashes: int64 CUDA out (out_capacity in hashes, default
+        out_hashes.numel()); results: CUDA out, 48 bytes a query
+        (segments.INDEX_RESULT_DTYPE); summary: int64 CUDA [6] out
+        (segments.INDEX_LOOKUP_SUMMARY_DTYPE).  out_hashes goes to
+        ReplayTable.read_hashes unchanged.  Asynchronous;
+        segments.index_lookup_hashes splits the reply on the host."""
+        nbytes = lambda x: 0 if x is None else x.numel() * x.element_size()
+        if qkeys_bytes is None:
+            qkeys_bytes = nbytes(qkeys)
+        if n_queries is None:
+            n_queries = nbytes(queries) // 40
+        if out_capacity is None:
+            out_capacity = nbytes(out_hashes) // 8
+        if nbytes(queries) < 40 * n_queries or nbytes(results) < 48 * n_queries:
+            raise RamcrcError("Context.index_lookup: queries or results are smaller than n_queries")
+        if nbytes(out_hashes) < 8 * out_capacity:
+            raise RamcrcError("Context.index_lookup: out_hashes is smaller than out_capacity")
+        if nbytes(summary) < 48 or nbytes(index.summary) < 56:
+            raise RamcrcError("Context.index_lookup: a summary is too small")
+        rc = lib().ramcrc_index_lookup_device(
+            self._h, _ptr(index.entries), _ptr(index.hashes), _ptr(index.index_keys), _ptr(index.summary),
+            _ptr(qkeys) if qkeys_bytes else None, int(qkeys_bytes), _ptr(queries) if n_queries else None,
+            int(n_queries), _ptr(out_hashes) if out_capacity else None, int(out_capacity),
+            _ptr(results) if n_queries else None, _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_index_lookup_device")
+        return out_hashes
 
     # All tensors below are CUDA tensors; outputs are int32 tensors holding the
     # uint32 CRC bit patterns.
@@ -1390,6 +1498,38 @@ class ReplayTable:
             _ptr(summary), _stream(stream))
         _check(rc, "ramcrc_replay_table_enumerate_device")
         return payload
+
+    def index_build(self, table_id, index_id, entries, hashes, index_keys, summary, entry_capacity=None,
+                    keys_capacity=None, stream=None):
+        """The sorted secondary index of table_id's key index_id (>= 1) over the
+        table's object winners, built on the device
+        (ramcrc_replay_table_index_build_device).  entries: CUDA out, 32 bytes
+        an entry (segments.INDEX_ENTRY_DTYPE), 16-byte aligned (entry_capacity
+        default: its bytes / 32); hashes: int64 CUDA [entry_capacity] out, the
+        dense copy of the entries' hashes; index_keys: uint8 CUDA out, the
+        index's own copy of its keys (keys_capacity default:
+        index_keys.numel()); summary: int64 CUDA [7] out
+        (segments.INDEX_BUILD_SUMMARY_DTYPE).  With the three arrays None and
+        both capacities 0 the call only sizes.  Read-only on the table.
+        Asynchronous.  Returns an Index holding the four tensors, for
+        Context.index_lookup."""
+        nbytes = lambda x: 0 if x is None else x.numel() * x.element_size()
+        if entry_capacity is None:
+            entry_capacity = min(nbytes(entries) // 32, nbytes(hashes) // 8)
+        if keys_capacity is None:
+            keys_capacity = nbytes(index_keys)
+        if nbytes(entries) < 32 * entry_capacity or nbytes(hashes) < 8 * entry_capacity:
+            raise RamcrcError("ReplayTable.index_build: entries or hashes are smaller than entry_capacity")
+        if nbytes(index_keys) < keys_capacity:
+            raise RamcrcError("ReplayTable.index_build: index_keys is smaller than keys_capacity")
+        if nbytes(summary) < 56:
+            raise RamcrcError("ReplayTable.index_build: summary is smaller than 56 bytes")
+        rc = lib().ramcrc_replay_table_index_build_device(
+            self._h, int(table_id), int(index_id), _ptr(entries) if entry_capacity else None,
+            int(entry_capacity), _ptr(hashes) if entry_capacity else None,
+            _ptr(index_keys) if keys_capacity else None, int(keys_capacity), _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_index_build_device")
+        return Index(entries, hashes, index_keys, summary)
 
     def write(self, data, reqs, out, out_cert, parts, summary, next_version, timestamp=0,
               rules=None, key_hash=None, batch_segment_id=None, refs=None, old=None,

@@ -94,6 +94,24 @@ ENUMERATE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "tombstones", "full", "stuck", "spoiled")])
 ENUM_KEYS_ONLY = 1
 ENUM_MAX_STALE = 8
+# ramcrc_index_entry, ramcrc_index_build_summary, ramcrc_index_query,
+# ramcrc_index_result and ramcrc_index_lookup_summary
+# (ramcrc_replay_table_index_build_device / _host, ramcrc_index_lookup_device /
+# _host); a query that was not answered has out_off = READ_NONE
+INDEX_ENTRY_DTYPE = np.dtype([("prefix", "<u8"), ("pk_hash", "<u8"), ("key_off", "<u8"),
+                              ("key_len", "<u4"), ("reserved", "<u4")])
+INDEX_BUILD_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "n_entries", "key_bytes", "entries_needed", "key_bytes_needed", "objects_seen", "overflow",
+    "spoiled")])
+INDEX_QUERY_DTYPE = np.dtype([("first_off", "<u8"), ("last_off", "<u8"), ("first_allowed_hash", "<u8"),
+                              ("first_len", "<u4"), ("last_len", "<u4"), ("max_hashes", "<u4"),
+                              ("reserved", "<u4")])
+INDEX_RESULT_DTYPE = np.dtype([("out_off", "<u8"), ("next_entry", "<u8"), ("next_key_hash", "<u8"),
+                               ("next_key_off", "<u8"), ("num_hashes", "<u4"), ("next_key_len", "<u4"),
+                               ("status", "<u4"), ("reserved", "<u4")])
+INDEX_LOOKUP_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "served", "hashes", "bad", "maxed_out", "n_entries", "overflow_index")])
+INDEX_OK, INDEX_BAD_QUERY, INDEX_NOT_SERVED = 0, 1, 2
 # ramcrc_write_req, ramcrc_write_ref, ramcrc_write_summary, the packed
 # MultiOp::Response::WritePart and ramcrc_seg_cert
 # (ramcrc_replay_table_write_device / _host)
@@ -326,6 +344,51 @@ def enum_frames(frames):
         if nb == 0 or nb & (nb - 1):
             raise ValueError("enum_frames: num_buckets must be a power of two")
     return a
+
+
+def index_queries(ranges, align=1):
+    """(key buffer uint8 [qkeys_bytes], queries INDEX_QUERY_DTYPE [n]) for a
+    list of (first key, last key, first_allowed_hash, max_hashes): the keys
+    packed one behind the other, each at a multiple of `align`.  An empty first
+    key is below every entry, an empty last key above."""
+    q = np.zeros(len(ranges), INDEX_QUERY_DTYPE)
+    parts, at = [], 0
+    for i, (first, last, first_allowed_hash, max_hashes) in enumerate(ranges):
+        offs = []
+        for key in (first, last):
+            pad = -at % align
+            offs.append(at + pad)
+            parts.append(b"\0" * pad + bytes(key))
+            at += pad + len(key)
+        q[i] = (offs[0], offs[1], int(first_allowed_hash), len(first), len(last), int(max_hashes), 0)
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), q
+
+
+def index_lookup_hashes(out_hashes, results, index_keys=None):
+    """A lookup's reply per query, from the packed hashes (uint64) and the
+    INDEX_RESULT_DTYPE results: a list of (status, hashes uint64 [num_hashes],
+    next key bytes or None: the range is exhausted, next_key_hash).  The next
+    key is read from index_keys (the index's key copy) when that is given,
+    else returned as (next_key_off, next_key_len).  A query that was not
+    answered gives (status, an empty array, None, 0)."""
+    out = np.ascontiguousarray(out_hashes).reshape(-1).view(np.uint64)
+    results = np.ascontiguousarray(results).reshape(-1).view(INDEX_RESULT_DTYPE)
+    keys = None if index_keys is None else np.ascontiguousarray(index_keys, np.uint8).reshape(-1)
+    reply = []
+    for r in results:
+        status = int(r["status"])
+        if status != INDEX_OK:
+            reply.append((status, np.zeros(0, np.uint64), None, 0))
+            continue
+        at, n = int(r["out_off"]), int(r["num_hashes"])
+        if at + n > out.size:
+            raise ValueError("index_lookup_hashes: a result points past the hashes")
+        nxt = None
+        if int(r["next_key_len"]):
+            o, ln = int(r["next_key_off"]), int(r["next_key_len"])
+            nxt = (o, ln) if keys is None else keys[o:o + ln].tobytes()
+        reply.append((status, out[at:at + n].copy(), nxt, int(r["next_key_hash"])))
+    return reply
 
 
 def tablets_array(rows):
