@@ -645,6 +645,38 @@ class ReplayTable {
         return batch;
     }
 
+    /// The source side of MasterService::migrateTablet
+    /// (src/MasterService.cc:1084-1225, over migrateSingleLogEntry,
+    /// :935-1073): the objects and tombstones of tableId whose key hash lies
+    /// in [firstKeyHash, lastKeyHash], from the batches `batches` (a host
+    /// array, in log order) starting at record startRecord of
+    /// batches[startIndex], are packed as Segment::append packs them into up
+    /// to maxSegments transfer segments of outCapacity bytes, output k at
+    /// d_out + k * outStride, each sealed with d_outCerts[k]; d_outCounts[k]
+    /// holds its entries.  flags: 0, or RAMCRC_MIGRATE_LIVE_ONLY to send only
+    /// the records that are their key's winner now.  d_sent (nullable,
+    /// sentCap entries) receives every sent entry's {batch, record},
+    /// d_segFirst (nullable) the index of every output's first entry.
+    /// d_summary carries the cursor for the next call (next_index,
+    /// next_record), done and too_large.  The receiving side is a walk of the
+    /// outputs under d_outCerts and an add() into the destination table.
+    /// Read-only on the table.
+    void
+    migrateTablet(const uint32_t* batches, uint32_t nBatches, uint64_t tableId, uint64_t firstKeyHash,
+                  uint64_t lastKeyHash, uint32_t flags, uint32_t startIndex, uint32_t startRecord,
+                  void* d_out, uint32_t outCapacity, uint64_t outStride, uint32_t maxSegments,
+                  ramcrc_seg_cert* d_outCerts, ramcrc_migrate_count* d_outCounts,
+                  ramcrc_replay_ref* d_sent, uint64_t sentCap, uint64_t* d_segFirst,
+                  ramcrc_migrate_summary* d_summary, void* stream = NULL)
+    {
+        check(ramcrc_replay_table_migrate_device(table, batches, nBatches, tableId, firstKeyHash,
+                                                 lastKeyHash, flags, startIndex, startRecord, d_out,
+                                                 outCapacity, outStride, maxSegments, d_outCerts,
+                                                 d_outCounts, d_sent, sentCap, d_segFirst, d_summary,
+                                                 stream),
+              "ramcrc_replay_table_migrate_device");
+    }
+
   private:
     static void
     check(int rc, const char* what)

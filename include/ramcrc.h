@@ -1908,6 +1908,137 @@ int ramcrc_replay_table_clean_host(ramcrc_replay_table_host* t, const uint32_t* 
                                    ramcrc_replay_ref* moved, ramcrc_clean_usage* usage,
                                    ramcrc_clean_summary* summary, uint32_t* batch);
 
+/* Migrating a tablet out of the table: the source half of MIGRATE_TABLET
+ * (MasterService::migrateTablet, src/MasterService.cc:1084-1225, over
+ * migrateSingleLogEntry, :935-1073).  The call scans listed batches in log
+ * order, keeps the objects and tombstones of one table id whose key hash lies
+ * in a range, and packs them into transfer segments, each sealed with its
+ * certificate.  The receiving side (receiveMigrationData, :1809-1878) is
+ * ramcrc_segment_walk_device under those certificates and then
+ * ramcrc_replay_table_add_device into the destination table.
+ *
+ * 1. Source order.  batches[0 .. n_batches) are batch numbers, read on the
+ *    host at the call.  RAMCRC_EINVAL before any launch when n_batches is 0, a
+ *    number repeats, or a batch was never added or was cleaned since the last
+ *    reset.  Records are taken batch by batch in the order given, within a
+ *    batch in record order: LogIterator's order.  The caller lists the batches
+ *    of the first pass and, in a later call, those added since (phases 1 and 3
+ *    of the reference).
+ * 2. Selection (:945-1013).  A record is selected when it was a participant
+ *    of its add (an OBJ or OBJTOMB, well formed, in a segment with
+ *    RAMCRC_SEG_OK), all 64 bits of its table id equal table_id, and its
+ *    record hash lies in [first_hash, last_hash], both ends included.  The
+ *    record hash is the one read_hashes and enumerate use: the hash the batch
+ *    was added with, or Key::getHash of the record's key where the batch has
+ *    none.  first_hash > last_hash selects nothing.  By default every selected
+ *    object and tombstone is sent whether or not it is its key's winner
+ *    (:1016-1036 says why).  Ours: with RAMCRC_MIGRATE_LIVE_ONLY only records
+ *    that are their key's winner now are sent -- clean's rule 2 unchanged, the
+ *    slot's pick names {batch, record}; the others count as skipped_dead.
+ *    Ours: records that never took part in their add -- RPCRESULT, PREP,
+ *    PREPTOMB, TXDECISION, TXPLIST and every other type, malformed and
+ *    overlong records, records of a segment without RAMCRC_SEG_OK -- are not
+ *    sent and count as skipped_other; they stay with the master, as clean and
+ *    add leave them aside.  The tests are made in this order (participant,
+ *    table id, range, winner) and a record counts under the first it fails.
+ *    Unknown flag bits are RAMCRC_EINVAL.
+ * 3. Transfer segments.  Output k lies at d_out + k * out_stride, holds
+ *    out_capacity bytes and starts empty.  Every sent record is laid out as
+ *    Segment::append(type, payload, length) lays it out: the header byte is
+ *    rebuilt with the minimal length bytes (a fresh EntryHeader), not copied
+ *    from the source; the payload is the source's, byte for byte.  Greedy cut:
+ *    an entry with head + 1 + lengthBytes + length > out_capacity closes the
+ *    current output and opens the next.  An entry that does not fit an empty
+ *    output stops the call before it (:1061-1065): too_large = 1, the cursor
+ *    names it, the outputs sealed so far are valid.  d_out_certs[k] = {head,
+ *    checksum} is what ramcrc_segments_certify_device returns for output k;
+ *    d_out_counts[k] = {entries, objects, tombstones, 0}.  No byte at or past
+ *    a head is written; outputs >= segments_used are untouched, their
+ *    certificates and counts included.
+ * 4. Cursor.  The call starts at record start_record of batches[start_index];
+ *    {n_batches, 0} is the cursor of a finished migration.  When max_segments
+ *    outputs are in use, the call stops before the first entry that would
+ *    open another.  The summary's next_index / next_record name the entry the
+ *    call stopped before ({n_batches, 0} and done = 1 at the end of the list);
+ *    every counter covers the records from the start cursor up to that entry,
+ *    so the counters of chained calls add up.  K calls of one output each,
+ *    chained by the cursor, write byte for byte what one call with K outputs
+ *    writes.  Where one entry stops the call for several reasons, too_large
+ *    is looked at first, then d_sent, then max_segments.  RAMCRC_EINVAL for
+ *    start_index > n_batches, start_index == n_batches with a record, or
+ *    start_record above that batch's entries_cap.
+ * 5. d_sent (nullable, sent_cap entries): for every sent entry in output order
+ *    its {batch, record}; d_seg_first[k] (nullable) is the index among them of
+ *    output k's first entry.  With d_sent given, the call stops before the
+ *    entry that would be number sent_cap, as a full output stops it: done = 0,
+ *    too_large = 0, no overflow.  sent_cap > 0 without d_sent is RAMCRC_EINVAL.
+ * 6. The table is read and nothing in it changes: no table word, no batch
+ *    number, nothing retired.  On a spoiled table only the summary is
+ *    written, zero with spoiled = 1.
+ * 7. Arguments.  RAMCRC_EINVAL before any launch for NULL t, batches or
+ *    d_summary; with max_segments > 0, NULL d_out_certs or d_out_counts, or
+ *    NULL d_out with out_capacity > 0; d_out not 16-byte aligned; out_capacity
+ *    or out_stride not a multiple of 16 (an output can become a batch's
+ *    segment at the destination); out_stride < out_capacity; out_capacity >
+ *    RAMCRC_MIGRATE_MAX_CAPACITY; max_segments > RAMCRC_MIGRATE_MAX_SEGMENTS;
+ *    misaligned structures (8 for 64-bit fields, 4 for certificates and
+ *    counts).  The outputs must not overlap any batch of the table; the call
+ *    cannot check this.
+ * 8. Stream-ordered, asynchronous, serialised by the handle like add.  The
+ *    launches follow n_batches, the listed batches' entries_cap and
+ *    max_segments, never a count the device knows, so the call chains without
+ *    a sync and can be captured.  Scratch comes from the context: with T the
+ *    sum over the listed batches of ceil(entries_cap / 256), after
+ *    ramcrc_ctx_reserve(ctx, 2 * (n_batches + 40 + 8 * max_segments + 8 * T),
+ *    128 * T) the call does not allocate.
+ *
+ * Stays with the master: the TabletManager test and STATUS_UNKNOWN_TABLET,
+ * prepForMigration and getHeadOfLog, LOCKED_FOR_MIGRATION and the epoch wait,
+ * reassignTabletOwnership, deleteTablet and removeOrphanedObjects, the
+ * transaction and RpcResult records, the transport. */
+#define RAMCRC_MIGRATE_LIVE_ONLY 1u
+#define RAMCRC_MIGRATE_MAX_CAPACITY (1u << 28)
+#define RAMCRC_MIGRATE_MAX_SEGMENTS 65536u
+
+typedef struct ramcrc_migrate_count {    /* one per output; 16 bytes */
+    uint32_t entries, objects, tombstones, reserved;
+} ramcrc_migrate_count;
+
+typedef struct ramcrc_migrate_summary {
+    uint64_t next_index, next_record;    /* the cursor of the next call */
+    uint64_t done;                       /* the list is exhausted */
+    uint64_t too_large;                  /* the entry at the cursor fits no empty output */
+    uint64_t segments_used;
+    uint64_t sent_objects, sent_tombstones;
+    uint64_t sent_bytes;                 /* entry bytes: header byte, length bytes, payload */
+    uint64_t payload_bytes;              /* totalBytes of :1039 */
+    uint64_t records_read;               /* from the start cursor up to the next */
+    uint64_t skipped_other, skipped_table, skipped_range, skipped_dead;
+    uint64_t spoiled;
+} ramcrc_migrate_summary;
+
+int ramcrc_replay_table_migrate_device(ramcrc_replay_table* t, const uint32_t* batches /* host */,
+                                       uint32_t n_batches, uint64_t table_id, uint64_t first_hash,
+                                       uint64_t last_hash, uint32_t flags, uint32_t start_index,
+                                       uint32_t start_record, void* d_out, uint32_t out_capacity,
+                                       uint64_t out_stride, uint32_t max_segments,
+                                       ramcrc_seg_cert* d_out_certs, ramcrc_migrate_count* d_out_counts,
+                                       ramcrc_replay_ref* d_sent /* nullable */, uint64_t sent_cap,
+                                       uint64_t* d_seg_first /* nullable */,
+                                       ramcrc_migrate_summary* d_summary, void* stream);
+
+/* The same on the host table, single-threaded: host pointers, no alignment
+ * rules for the structures, the same bytes.  start_record is held against the
+ * batch's record count. */
+int ramcrc_replay_table_migrate_host(ramcrc_replay_table_host* t, const uint32_t* batches,
+                                     uint32_t n_batches, uint64_t table_id, uint64_t first_hash,
+                                     uint64_t last_hash, uint32_t flags, uint32_t start_index,
+                                     uint32_t start_record, void* out, uint32_t out_capacity,
+                                     uint64_t out_stride, uint32_t max_segments,
+                                     ramcrc_seg_cert* out_certs, ramcrc_migrate_count* out_counts,
+                                     ramcrc_replay_ref* sent, uint64_t sent_cap, uint64_t* seg_first,
+                                     ramcrc_migrate_summary* summary);
+
 /* The side log of a replay: what ObjectManager::replaySegment hands to
  * sideLog->append for every record it keeps (src/ObjectManager.cc:720-734,
  * :840-867), and where each record then lies.  The call is

@@ -23,13 +23,14 @@ SOURCES = ["ramcrc_device.hip", "ramcrc_host.cc", "ramcrc_shard.hip", "ramcrc_fi
 HEADERS = ["gf2.h", "walk_rules.h", "shard_plan.h", "murmur3.h", "partition_rules.h",
            "resolve_rules.h", "sidelog_rules.h", "lookup_rules.h", "read_rules.h",
            "write_rules.h", "remove_rules.h", "increment_rules.h", "clean_rules.h",
-           "read_hashes_rules.h", "enumerate_rules.h", "index_rules.h",
+           "read_hashes_rules.h", "enumerate_rules.h", "index_rules.h", "migrate_rules.h",
            # parts of ramcrc_device.hip (one translation unit)
            "dev_common.inc", "dev_chunks.inc", "dev_bins.inc", "dev_entries.inc",
            "dev_plan.inc", "dev_host.inc", "dev_walk.inc", "dev_checks.inc",
            "dev_append.inc", "dev_sidelog.inc", "dev_partition.inc", "dev_resolve.inc",
            "dev_replay_table.inc", "dev_write.inc", "dev_remove.inc", "dev_increment.inc",
-           "dev_clean.inc", "dev_read_hashes.inc", "dev_enumerate.inc", "dev_index.inc"]
+           "dev_clean.inc", "dev_read_hashes.inc", "dev_enumerate.inc", "dev_index.inc",
+           "dev_migrate.inc"]
 
 
 def hipcc():

@@ -66,6 +66,7 @@
 //   dev_read_hashes.inc   k_rh_* (an indexed read's reply: objects by primary-key hash)
 //   dev_enumerate.inc     k_en_* (one reply of a table enumeration: a walk over the buckets)
 //   dev_index.inc         k_ix_*, k_ixl_* (a secondary index: sorted entries and range lookups)
+//   dev_migrate.inc       k_mig_* (a tablet migration: filtered log-order scan into transfer segments)
 // This file keeps the extern "C" entry points of include/ramcrc.h.
 //
 // No MFMA: this is a byte scan, bound by HBM reads.
@@ -95,6 +96,7 @@
 #include "remove_rules.h"
 #include "increment_rules.h"
 #include "clean_rules.h"
+#include "migrate_rules.h"
 #include "ramcrc.h"
 
 namespace {
@@ -125,6 +127,7 @@ using ramcrc::OpTable;
 #include "dev_remove.inc"
 #include "dev_increment.inc"
 #include "dev_clean.inc"
+#include "dev_migrate.inc"
 
 extern "C" {
 
@@ -2263,6 +2266,121 @@ int ramcrc_replay_table_clean_device(ramcrc_replay_table* t, const uint32_t* vic
     const CleanOut o{d_out, out_capacity, d_out_cert, d_out_status, d_out_entries, out_entries_cap,
                      d_out_n_entries, d_out_work, d_moved, batch};
     return clean_impl(t, victims, n_victims, &o, d_usage, d_summary, stream);
+}
+
+int ramcrc_replay_table_migrate_device(ramcrc_replay_table* t, const uint32_t* batches, uint32_t n_batches,
+                                       uint64_t table_id, uint64_t first_hash, uint64_t last_hash,
+                                       uint32_t flags, uint32_t start_index, uint32_t start_record,
+                                       void* d_out, uint32_t out_capacity, uint64_t out_stride,
+                                       uint32_t max_segments, ramcrc_seg_cert* d_out_certs,
+                                       ramcrc_migrate_count* d_out_counts, ramcrc_replay_ref* d_sent,
+                                       uint64_t sent_cap, uint64_t* d_seg_first,
+                                       ramcrc_migrate_summary* d_summary, void* stream)
+{
+    if (!t || !batches || !d_summary || n_batches == 0 || (flags & ~ramcrc_mig::kKnownFlags))
+        return RAMCRC_EINVAL;
+    const uint64_t O = reinterpret_cast<uint64_t>(d_out);
+    if ((reinterpret_cast<uint64_t>(d_summary) & 7) || (O & 15) || (out_capacity & 15) || (out_stride & 15) ||
+        out_stride < out_capacity || out_capacity > RAMCRC_MIGRATE_MAX_CAPACITY ||
+        max_segments > RAMCRC_MIGRATE_MAX_SEGMENTS ||
+        (max_segments && (!d_out_certs || !d_out_counts || (out_capacity && !d_out))) ||
+        (out_stride && max_segments > (UINT64_MAX - O) / out_stride) ||
+        (reinterpret_cast<uint64_t>(d_out_certs) & 3) || (reinterpret_cast<uint64_t>(d_out_counts) & 3) ||
+        (reinterpret_cast<uint64_t>(d_sent) & 7) || (reinterpret_cast<uint64_t>(d_seg_first) & 7) ||
+        (sent_cap && !d_sent) || start_index > n_batches || (start_index == n_batches && start_record))
+        return RAMCRC_EINVAL;
+    std::lock_guard<std::mutex> lt(t->mu);
+    // the list: numbered, not cleaned, none twice; the tiles from the cursor on
+    std::vector<uint64_t> list;
+    uint64_t ntiles = 0;
+    try {
+        std::vector<uint8_t> seen(t->ecap.size(), 0);
+        list.reserve(uint64_t(n_batches) + 1);
+        for (uint32_t v = 0; v < n_batches; v++) {
+            const uint32_t b = batches[v];
+            if (b >= t->ecap.size() || t->retired[b] || seen[b])
+                return RAMCRC_EINVAL;
+            seen[b] = 1;
+            if (v < start_index)
+                continue;
+            uint64_t n = t->ecap[b];
+            if (v == start_index) {
+                if (start_record > n)
+                    return RAMCRC_EINVAL;
+                n -= uint64_t(start_record) & ~uint64_t(kPartThreads - 1);
+            }
+            list.push_back((uint64_t(b) << 48) | ntiles);
+            ntiles += (n + kPartThreads - 1) / kPartThreads;
+        }
+        list.push_back(ntiles);
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    if (ntiles > kClFirstMask)
+        return RAMCRC_EINVAL;
+    ramcrc_ctx* c = t->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // scratch, in the chunk-partial buffer: the list, the head line, the
+    // boundaries, a line per tile; in the plan buffer a word per record
+    // (ramcrc.h states these sizes)
+    const uint64_t list_words = (uint64_t(list.size()) + 15) & ~15ull;
+    const uint64_t bound_words = uint64_t(kMgBoundWords) * (uint64_t(max_segments) + 1);
+    int rc = reserve_locked(c, 2 * (uint64_t(n_batches) + 40 + 8 * uint64_t(max_segments) + kMgTileWords * ntiles),
+                            (kPartThreads / 2) * ntiles);
+    if (rc)
+        return rc;
+    const RtabDesc a = rtab_desc(t);
+    MgDesc d{};
+    d.nlist = list.size() - 1;
+    d.ntiles = ntiles;
+    uint64_t* const d_list = reinterpret_cast<uint64_t*>(c->partials);
+    d.list = d_list;
+    d.head = d_list + list_words;
+    d.bound = d.head + kMgHeadWords;
+    d.tile = d.bound + bound_words;
+    d.rec = reinterpret_cast<uint32_t*>(c->plan_local);
+    d.table_id = table_id;
+    d.first_hash = first_hash;
+    d.last_hash = last_hash;
+    d.flags = flags;
+    d.start_index = start_index;
+    d.start_record = start_record;
+    d.n_batches = n_batches;
+    d.out = O;
+    d.cap = out_capacity;
+    d.stride = out_stride;
+    d.max_segments = max_segments;
+    d.certs = d_out_certs;
+    d.counts = d_out_counts;
+    d.sent = reinterpret_cast<uint2*>(d_sent);
+    d.sent_cap = sent_cap;
+    d.seg_first = d_seg_first;
+    d.summary = d_summary;
+    // the list travels in the kernels' arguments, as clean's does
+    for (uint64_t f = 0; f < list.size(); f += kClOpenMax) {
+        ClOpen op;
+        op.vic = d_list;
+        op.first = f;
+        op.n = uint32_t(list.size() - f < kClOpenMax ? list.size() - f : kClOpenMax);
+        memcpy(op.w, list.data() + f, op.n * sizeof(uint64_t));
+        hipLaunchKernelGGL(k_clean_open, dim3(1), dim3(kClOpenMax), 0, s, op);
+        HIPCHK(hipGetLastError());
+    }
+    const dim3 grid(rtab_grid(c, ntiles * kPartThreads, kPartThreads));
+    hipLaunchKernelGGL(k_mig_size, grid, dim3(kPartThreads), 0, s, a, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_mig_cut, dim3(1), dim3(kPartThreads), 0, s, a, d);
+    HIPCHK(hipGetLastError());
+    if (max_segments) {
+        hipLaunchKernelGGL(k_mig_emit, grid, dim3(kPartThreads), 0, s, a, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_mig_seal, dim3(rtab_grid(c, max_segments, kPartThreads)), dim3(kPartThreads), 0, s,
+                           a, d);
+        HIPCHK(hipGetLastError());
+    }
+    return RAMCRC_OK;
 }
 
 int ramcrc_verify_objects_device(ramcrc_ctx* c, const void* d_base, uint64_t seg_stride,

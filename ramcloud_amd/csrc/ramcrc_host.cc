@@ -38,6 +38,7 @@
 #include "remove_rules.h"
 #include "increment_rules.h"
 #include "clean_rules.h"
+#include "migrate_rules.h"
 
 namespace {
 
@@ -2085,6 +2086,143 @@ int ramcrc_replay_table_clean_host(ramcrc_replay_table_host* t, const uint32_t* 
 {
     return clean_host(t, victims, n_victims, false, out, out_capacity, out_cert, out_status, out_entries,
                       out_entries_cap, out_n_entries, out_work, moved, usage, summary, batch);
+}
+
+// A tablet migration (the rules of migrate_rules.h): the listed batches'
+// records in order from the cursor, each classified, the sent ones appended to
+// the current output until one closes it.
+int ramcrc_replay_table_migrate_host(ramcrc_replay_table_host* t, const uint32_t* batches,
+                                     uint32_t n_batches, uint64_t table_id, uint64_t first_hash,
+                                     uint64_t last_hash, uint32_t flags, uint32_t start_index,
+                                     uint32_t start_record, void* out, uint32_t out_capacity,
+                                     uint64_t out_stride, uint32_t max_segments,
+                                     ramcrc_seg_cert* out_certs, ramcrc_migrate_count* out_counts,
+                                     ramcrc_replay_ref* sent, uint64_t sent_cap, uint64_t* seg_first,
+                                     ramcrc_migrate_summary* summary)
+{
+    namespace mg = ramcrc_mig;
+    namespace cl = ramcrc_clean;
+    typedef ramcrc_replay_table_host::Batch Batch;
+    if (!t || !batches || !summary || n_batches == 0 || (flags & ~mg::kKnownFlags))
+        return RAMCRC_EINVAL;
+    if ((out_capacity & 15) || (out_stride & 15) || out_stride < out_capacity ||
+        out_capacity > RAMCRC_MIGRATE_MAX_CAPACITY || max_segments > RAMCRC_MIGRATE_MAX_SEGMENTS ||
+        (max_segments && (!out_certs || !out_counts || (out_capacity && !out))) || (sent_cap && !sent) ||
+        start_index > n_batches || (start_index == n_batches && start_record))
+        return RAMCRC_EINVAL;
+    try {
+        std::vector<uint8_t> seen(t->batches.size(), 0);
+        for (uint32_t v = 0; v < n_batches; v++) {
+            const uint32_t b = batches[v];
+            if (b >= t->batches.size() || t->batches[b].retired || seen[b])
+                return RAMCRC_EINVAL;
+            seen[b] = 1;
+        }
+    } catch (...) {
+        return RAMCRC_ENOMEM;
+    }
+    if (start_index < n_batches && start_record > t->batches[batches[start_index]].n)
+        return RAMCRC_EINVAL;
+    ramcrc_migrate_summary sm{};
+    if (t->spoiled) {
+        sm.spoiled = 1;
+        memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+        return RAMCRC_OK;
+    }
+    uint8_t* const ob = static_cast<uint8_t*>(out);
+    bool open = false;           // output segments_used - 1 takes entries
+    uint64_t head = 0;
+    uint32_t meta = 0;           // its running header checksum
+    ramcrc_migrate_count cnt{};
+    const auto seal = [&]() {
+        uint8_t lenle[4];
+        for (int k = 0; k < 4; k++)
+            lenle[k] = uint8_t(uint32_t(head) >> (8 * k));
+        const ramcrc_seg_cert cert{uint32_t(head), ~ramcrc_update(meta, lenle, 4)};   // Segment::getAppendedLength
+        const uint64_t k = sm.segments_used - 1;
+        memcpy(reinterpret_cast<uint8_t*>(out_certs) + k * sizeof(cert), &cert, sizeof(cert));
+        memcpy(reinterpret_cast<uint8_t*>(out_counts) + k * sizeof(cnt), &cnt, sizeof(cnt));
+    };
+    sm.next_index = n_batches;
+    sm.done = 1;
+    for (uint32_t v = start_index; v < n_batches && sm.done; v++) {
+        const uint32_t b = batches[v];
+        const Batch& bt = t->batches[b];
+        for (uint64_t i = v == start_index ? start_record : 0; i < bt.n; i++) {
+            ramcrc_seg_entry r;   // (a survivor's table has no alignment rule)
+            memcpy(&r, reinterpret_cast<const uint8_t*>(bt.entries) + i * sizeof(r), sizeof(r));
+            uint64_t w;
+            memcpy(&w, reinterpret_cast<const uint8_t*>(bt.work) + i * sizeof(w), sizeof(w));
+            const bool part = w != cl::kNoSlot;
+            const uint32_t po = r.offset + 1 + ((r.header >> 6) & 3) + 1;
+            const LookRd rd{bt.base + r.segment * bt.stride + po};
+            uint64_t table = 0, hash = 0;
+            bool winner = false;
+            if (part) {
+                const ramcrc_part::Parsed p = ramcrc_part::parse(r.header & 0x3f, r.length, true, rd);
+                table = p.table_id;
+                if (table == table_id) {
+                    if (bt.key_hash)
+                        memcpy(&hash, reinterpret_cast<const uint8_t*>(bt.key_hash) + i * 8, 8);
+                    else
+                        hash = ramcrc::key_hash(p.table_id, rd.pay + p.key_off, p.key_len);
+                    winner = cl::live(w, t->slots[w].rank, b, i);
+                }
+            }
+            const uint32_t k = mg::classify(part, r.header, table, table_id, hash, first_hash, last_hash, flags, winner);
+            if (mg::sent(k)) {
+                const uint64_t size = mg::entry_bytes(r.length);
+                const bool stop = mg::too_large(size, out_capacity) || (sent && sm.sent_objects + sm.sent_tombstones == sent_cap) ||
+                                  ((!open || mg::closes(head, size, out_capacity)) && sm.segments_used == max_segments);
+                if (stop) {
+                    sm.too_large = mg::too_large(size, out_capacity);
+                    sm.next_index = v;
+                    sm.next_record = i;
+                    sm.done = 0;
+                    break;
+                }
+                if (!open || mg::closes(head, size, out_capacity)) {
+                    if (open)
+                        seal();
+                    if (seg_first) {
+                        const uint64_t f = sm.sent_objects + sm.sent_tombstones;
+                        memcpy(reinterpret_cast<uint8_t*>(seg_first) + sm.segments_used * 8, &f, 8);
+                    }
+                    sm.segments_used++;
+                    open = true;
+                    head = 0;
+                    meta = 0xFFFFFFFFu;
+                    cnt = ramcrc_migrate_count{};
+                }
+                uint8_t* const at = ob + (sm.segments_used - 1) * out_stride + head;
+                const uint32_t nm = mg::meta_bytes(r.length);
+                for (uint32_t q = 0; q < nm; q++)
+                    at[q] = uint8_t(mg::meta_byte(r.header, r.length, q));
+                meta = ramcrc_update(meta, at, nm);
+                memcpy(at + nm, rd.pay, r.length);
+                if (sent) {
+                    const ramcrc_replay_ref ref{b, uint32_t(i)};
+                    memcpy(reinterpret_cast<uint8_t*>(sent) + (sm.sent_objects + sm.sent_tombstones) * sizeof(ref),
+                           &ref, sizeof(ref));
+                }
+                head += size;
+                cnt.entries++;
+                (k == mg::kSentObject ? cnt.objects : cnt.tombstones)++;
+                (k == mg::kSentObject ? sm.sent_objects : sm.sent_tombstones)++;
+                sm.sent_bytes += size;
+                sm.payload_bytes += r.length;
+            }
+            sm.records_read++;
+            sm.skipped_other += k == mg::kSkippedOther;
+            sm.skipped_table += k == mg::kSkippedTable;
+            sm.skipped_range += k == mg::kSkippedRange;
+            sm.skipped_dead += k == mg::kSkippedDead;
+        }
+    }
+    if (open)
+        seal();
+    memcpy(reinterpret_cast<uint8_t*>(summary), &sm, sizeof(sm));   // (no alignment rule)
+    return RAMCRC_OK;
 }
 
 }  // extern "C"

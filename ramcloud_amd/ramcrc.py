@@ -153,6 +153,10 @@ def lib():
         "ramcrc_replay_table_clean_size_host": (i32, [vp, vp, u32, vp, vp]),
         "ramcrc_replay_table_clean_host": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u64, vp, vp, vp,
                                                  vp, vp, _c.POINTER(u32)]),
+        "ramcrc_replay_table_migrate_device": (i32, [vp, vp, u32, u64, u64, u64, u32, u32, u32, vp, u32, u64,
+                                                     u32, vp, vp, vp, u64, vp, vp, vp]),
+        "ramcrc_replay_table_migrate_host": (i32, [vp, vp, u32, u64, u64, u64, u32, u32, u32, vp, u32, u64,
+                                                   u32, vp, vp, vp, u64, vp, vp]),
         "ramcrc_segment_fill_objects": (i32, [vp, u32, u32, u64, _c.POINTER(u32), vp]),
         "ramcrc_assemble_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "ramcrc_assemble_objects_host": (i32, [vp, vp, vp, u64]),
@@ -919,6 +923,53 @@ class ReplayTableHost:
                 e.outputs = res
             raise
         return res
+
+    def migrate(self, batches, table_id, out_capacity, max_segments, first_hash=0,
+                last_hash=0xFFFFFFFFFFFFFFFF, live_only=False, start=(0, 0), out_stride=None,
+                want_sent=True, sent_cap=None, fill=0, flags=None):
+        """Migrate a tablet out of the table (ramcrc_replay_table_migrate_host):
+        the objects and tombstones of table_id with a record hash in
+        [first_hash, last_hash], from the listed batches in order from the
+        cursor `start` = (list index, record), packed into at most max_segments
+        transfer segments of out_capacity bytes.  Returns a dict: out (uint8
+        [max_segments, out_stride]), certs (segments.CERT_DTYPE [max_segments]),
+        counts (segments.MIGRATE_COUNT_DTYPE [max_segments]), sent
+        (segments.REPLAY_REF_DTYPE [sent_cap] or None), seg_first (uint64
+        [max_segments]), summary (a segments.MIGRATE_SUMMARY_DTYPE scalar).
+        Every output array starts as bytes of `fill`; the table does not
+        change."""
+        from . import segments as _seg
+        batches = np.ascontiguousarray(batches, np.uint32).reshape(-1)
+        stride = int(out_capacity if out_stride is None else out_stride)
+        nseg = int(max_segments)
+        if flags is None:
+            flags = MIGRATE_LIVE_ONLY if live_only else 0
+
+        def mk(shape, dt):
+            nbytes = int(np.prod(shape)) * np.dtype(dt).itemsize
+            return np.full(nbytes, fill, np.uint8).view(dt).reshape(shape)
+
+        if want_sent and sent_cap is None:
+            sent_cap = sum(self._keep[int(b)][2].shape[0] for b in batches
+                           if int(b) < len(self._keep) and self._keep[int(b)] is not None)
+        out = mk((nseg, stride), np.uint8)
+        certs = mk((nseg,), _seg.CERT_DTYPE)
+        counts = mk((nseg,), _seg.MIGRATE_COUNT_DTYPE)
+        sent = mk((int(sent_cap),), _seg.REPLAY_REF_DTYPE) if want_sent else None
+        seg_first = mk((nseg,), np.uint64)
+        summary = mk((1,), _seg.MIGRATE_SUMMARY_DTYPE)
+        p = lambda a: _c.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        rc = lib().ramcrc_replay_table_migrate_host(
+            self._h, p(batches), batches.size, int(table_id), int(first_hash), int(last_hash), int(flags),
+            int(start[0]), int(start[1]), p(out), int(out_capacity), stride, nseg, p(certs), p(counts),
+            _c.c_void_p(sent.ctypes.data) if sent is not None else None,
+            int(sent_cap) if want_sent else 0, p(seg_first), _c.c_void_p(summary.ctypes.data))
+        _check(rc, "ramcrc_replay_table_migrate_host")
+        return dict(out=out, certs=certs, counts=counts, sent=sent, seg_first=seg_first,
+                    summary=summary[0])
+
+
+MIGRATE_LIVE_ONLY = 1
 
 
 # ---------------------------------------------------------------- device
@@ -1734,6 +1785,67 @@ class ReplayTable:
             self._keep[int(b)] = None
         self._keep.append((out, out_status, out_entries, out_n_entries, None, out_work))
         return batch.value
+
+    @staticmethod
+    def migrate_reserve(entries_caps, max_segments):
+        """The (max_chunks, max_entries) arguments of Context.reserve after
+        which migrate over listed batches of these record-table capacities into
+        max_segments outputs does not allocate (include/ramcrc.h, rule 8)."""
+        caps = [int(x) for x in entries_caps]
+        tiles = sum((x + 255) // 256 for x in caps)
+        return 2 * (len(caps) + 40 + 8 * int(max_segments) + 8 * tiles), 128 * tiles
+
+    def migrate(self, batches, table_id, out, out_capacity, max_segments, out_certs, out_counts, summary,
+                first_hash=0, last_hash=0xFFFFFFFFFFFFFFFF, live_only=False, start=(0, 0),
+                out_stride=None, sent=None, sent_cap=None, seg_first=None, flags=None, stream=None):
+        """Migrate a tablet out of the table on the device
+        (ramcrc_replay_table_migrate_device): the objects and tombstones of
+        table_id with a record hash in [first_hash, last_hash], from the listed
+        batches in order from the cursor `start` = (list index, record), packed
+        into at most max_segments transfer segments.  out: uint8 CUDA, 16-byte
+        aligned, output k at k * out_stride (default out_capacity; both
+        multiples of 16); out_certs: int32 CUDA [max_segments, 2]; out_counts:
+        int32 CUDA [max_segments, 4] (segments.MIGRATE_COUNT_DTYPE); summary:
+        int64 CUDA [15] (segments.MIGRATE_SUMMARY_DTYPE); sent: int32 CUDA
+        [sent_cap, 2] out (segments.REPLAY_REF_DTYPE) or None; seg_first: int64
+        CUDA [max_segments] out or None.  The table does not change.
+        Asynchronous; chain calls with the summary's cursor."""
+        lst = np.ascontiguousarray(batches, np.uint32).reshape(-1)
+        nbytes = lambda x: x.numel() * x.element_size()
+        nseg = int(max_segments)
+        stride = int(out_capacity if out_stride is None else out_stride)
+        if flags is None:
+            flags = MIGRATE_LIVE_ONLY if live_only else 0
+        if nseg and out_capacity and (out is None or nbytes(out) < (nseg - 1) * stride + int(out_capacity)):
+            raise RamcrcError("ReplayTable.migrate: out is smaller than its geometry")
+        if sent is not None and sent_cap is None:
+            sent_cap = nbytes(sent) // 8
+        if sent is not None and nbytes(sent) < 8 * int(sent_cap):
+            raise RamcrcError("ReplayTable.migrate: sent is smaller than sent_cap")
+        for name, x, need in (("out_certs", out_certs, 8 * nseg), ("out_counts", out_counts, 16 * nseg),
+                              ("seg_first", seg_first, 8 * nseg), ("summary", summary, 120)):
+            if x is not None and nbytes(x) < need:
+                raise RamcrcError(f"ReplayTable.migrate: {name} is too small")
+        rc = lib().ramcrc_replay_table_migrate_device(
+            self._h, _c.c_void_p(lst.ctypes.data) if lst.size else None, lst.size, int(table_id),
+            int(first_hash), int(last_hash), int(flags), int(start[0]), int(start[1]),
+            _ptr(out) if nseg and out_capacity else None, int(out_capacity), stride, nseg, _ptr(out_certs),
+            _ptr(out_counts), _ptr(sent), int(sent_cap or 0) if sent is not None else 0, _ptr(seg_first),
+            _ptr(summary), _stream(stream))
+        _check(rc, "ramcrc_replay_table_migrate_device")
+        return summary
+
+    def receive_migration(self, data, seg_stride, seg_capacity, nseg, certs, status, entries, n_entries, work,
+                          stream=None):
+        """The receiving side of a migration (receiveMigrationData): walk the
+        nseg transfer segments in `data` under their certificates
+        (Context.segment_walk) and add them to this table (add).  status,
+        entries, n_entries: the walk's tables, out; work as add takes it.
+        Returns the batch number.  Asynchronous; a segment whose certificate
+        does not match takes no part, and shows in status."""
+        self._ctx.segment_walk(data, seg_stride, seg_capacity, nseg, certs, status, entries, n_entries,
+                               stream=stream)
+        return self.add(data, seg_stride, nseg, status, entries, n_entries, work, stream=stream)
 
 
 # ------------------------------------------------------------ multi-GPU shard

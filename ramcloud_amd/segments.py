@@ -150,7 +150,16 @@ CLEAN_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
     "victims", "records", "moved_objects", "moved_tombstones", "object_bytes", "tombstone_bytes",
     "dropped_objects", "dropped_tombstones", "dropped_other", "needed_bytes", "needed_records",
     "out_bytes", "batch", "spoiled")])
-CERT_DTYPE = np.dtype([("head", "<u4"), ("checksum", "<u4")])
+# ramcrc_migrate_count and ramcrc_migrate_summary (ramcrc_replay_table_migrate_device / _host)
+MIGRATE_COUNT_DTYPE = np.dtype([(n, "<u4") for n in ("entries", "objects", "tombstones", "reserved")])
+MIGRATE_SUMMARY_DTYPE = np.dtype([(n, "<u8") for n in (
+    "next_index", "next_record", "done", "too_large", "segments_used", "sent_objects",
+    "sent_tombstones", "sent_bytes", "payload_bytes", "records_read", "skipped_other",
+    "skipped_table", "skipped_range", "skipped_dead", "spoiled")])
+MIGRATE_LIVE_ONLY = 1
+MIGRATE_MAX_CAPACITY = 1 << 28
+MIGRATE_MAX_SEGMENTS = 65536
+CERT_DTYPE =np.dtype([("head", "<u4"), ("checksum", "<u4")])
 STATUS_RETRY = 17
 # ramcrc_log_ref, ramcrc_sidelog_counts and the not-appended mark
 # (ramcrc_replay_sidelog_device / _host)
@@ -326,6 +335,29 @@ def enumerate_objects(payload, payload_bytes):
             raise ValueError("enumerate_objects: the payload ends inside an object")
         out.append(raw[at:at + length])
         at += length
+    return out
+
+
+def migrate_entries(segment, head):
+    """The entries of a transfer segment (bytes or a uint8 array) whose
+    certificate's length is `head`, as a list of (type, payload bytes):
+    Segment's layout, a header byte (type | length bytes - 1 << 6), the
+    little-endian length, the payload."""
+    raw = np.ascontiguousarray(segment, np.uint8).reshape(-1).tobytes() \
+        if not isinstance(segment, (bytes, bytearray)) else bytes(segment)
+    end = int(head)
+    if end > len(raw):
+        raise ValueError("migrate_entries: head is past the segment")
+    out, at = [], 0
+    while at < end:
+        lb = (raw[at] >> 6) + 1
+        if at + 1 + lb > end:
+            raise ValueError("migrate_entries: the segment ends inside an entry header")
+        length = int.from_bytes(raw[at + 1:at + 1 + lb], "little")
+        if at + 1 + lb + length > end:
+            raise ValueError("migrate_entries: the segment ends inside a payload")
+        out.append((raw[at] & 0x3F, raw[at + 1 + lb:at + 1 + lb + length]))
+        at += 1 + lb + length
     return out
 
 
